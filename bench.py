@@ -9,14 +9,23 @@ forward + pinball loss + backward + gradient all-reduce + fused Adam step.
 The step itself is engine/step.py's TrainStep — the exact code path
 Trainer runs, not a bench-only reimplementation.
 
-After the timed region (single-process GPU runs) a 50-epoch accuracy probe
-at the reference training config (50 epochs / batch 32 / split .40 /
-window 60 — reference: resource-estimation/estimate.py:13-18) reports the
-prediction-MAE half of the metric: mean median absolute error for the
-RESRC / COMP / DEEPR estimators (reference: estimate.py:112-122).
+A plain run sets up, warms up, times the K steps and prints the result line.
+With --full (single-process GPU runs) a 50-epoch accuracy probe at the
+reference training config (50 epochs / batch 32 / split .40 / window 60 —
+reference: resource-estimation/estimate.py:13-18) follows the timed region
+and reports the prediction-MAE half of the metric: mean median absolute
+error for the RESRC / COMP / DEEPR estimators (reference:
+estimate.py:112-122).
+
+--dump-outputs DIR writes what the last timed step computed (loss, model
+output, gradients, updated parameters) as DIR/<name>.npy in float32.  The
+inputs and the initial weights are seeded, and model and optimizer are
+rewound to their initial state just before that step (outside the clock),
+so the arrays do not carry the reduction-order noise of the steps before
+and two builds can be compared array for array.
 
 Usage (driver):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints exactly one JSON line with the whole-job aggregate.
@@ -72,11 +81,79 @@ def parse_args():
     p.add_argument("--seq-len", type=int, default=60)
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--device", type=str, default=None)
-    # MAE half of the headline metric: auto = run on single-process GPU
-    # benches (the driver's N=1 run), skip in scale runs and on CPU
+    # a plain run does only what the headline figure needs; --full adds the
+    # accuracy probe after the timed region
+    p.add_argument("--full", action="store_true",
+                   help="also run the accuracy probe (see --accuracy)")
+    # MAE half of the headline metric, under --full only: auto = run on
+    # single-process GPU benches (the N=1 run), skip in scale runs and on CPU
     p.add_argument("--accuracy", choices=["auto", "on", "off"], default="auto")
     p.add_argument("--accuracy-epochs", type=int, default=50)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/*.npy")
     return p.parse_args()
+
+
+# --dump-outputs budget: 64 MB in all -> three float32 arrays of at most
+# 4M elements each (48 MB) plus the scalar loss
+_DUMP_MAX_ELEMS = 4 * 1024 * 1024
+
+
+def rewind_training_state(model: torch.nn.Module, opt, init_state) -> None:
+    """Put model and optimizer back, in place, to where they stood before
+    the first step (weights as seeded, Adam moments and step count zero).
+
+    --dump-outputs does this just before the last timed step.  The backward
+    kernels accumulate with fp32 atomics whose order varies; one step turns
+    that into a ~1e-5 relative difference of the gradients, and bf16
+    rounding plus Adam's early steps amplify it along a trajectory
+    (measured after 25 steps: 3e-2 on the gradients, 4e-3 on the loss).
+    From the rewound state the written arrays depend on the seeded inputs
+    and the kernels alone, so two runs agree to rounding."""
+    with torch.no_grad():
+        for k, v in model.state_dict().items():
+            v.copy_(init_state[k])
+        for st in opt.state.values():
+            st["exp_avg"].zero_()
+            st["exp_avg_sq"].zero_()
+            st["step"] = 0
+        step_t = getattr(opt, "_step_t", None)
+        if step_t is not None:      # capturable: device-side step counter
+            step_t.zero_()
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, model: torch.nn.Module,
+                 out: torch.Tensor | None = None) -> None:
+    """Write what the last timed step computed: the loss it returned, the
+    model output behind it (eager steps only), the gradients it left and
+    the parameters it updated, each flattened (parameters and gradients in
+    named_parameters order).  Arrays above the element budget are cut to a
+    fixed seeded sample, the same indices in every run."""
+    import numpy as np
+
+    def sample(flat: torch.Tensor) -> "np.ndarray":
+        flat = flat.detach().reshape(-1)
+        if flat.numel() > _DUMP_MAX_ELEMS:
+            gen = torch.Generator().manual_seed(20240229)
+            idx = torch.randint(flat.numel(), (_DUMP_MAX_ELEMS,),
+                                generator=gen).sort().values
+            flat = flat[idx.to(flat.device)]
+        return flat.float().cpu().numpy()
+
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu().numpy(),
+        "params": sample(torch.cat([p.detach().reshape(-1).float()
+                                    for p in params])),
+        "grads": sample(torch.cat([
+            (p.grad if p.grad is not None else torch.zeros_like(p))
+            .detach().reshape(-1).float() for p in params])),
+    }
+    if out is not None:
+        arrays["output"] = sample(out)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def build_train_tensors(args):
@@ -260,6 +337,10 @@ def main():
         # start identical or averaged gradients never reconcile them
         dist_ctx.broadcast_parameters(model)
     opt = FusedAdam(model.parameters(), lr=1e-3, capturable=on_gpu)
+    init_state = None
+    if args.dump_outputs:
+        init_state = {k: v.detach().clone()
+                      for k, v in model.state_dict().items()}
 
     n = X.shape[0]
     B = args.batch
@@ -310,7 +391,15 @@ def main():
         s = ((i + 3 * rank) * B + rank * 17) % max(n - B, 1)
         return step(X[s : s + B], y[s : s + B])
 
+    # --dump-outputs: keep a reference to the model output of the latest
+    # eager step (a graph replay runs no Python forward, so none there)
+    last_out = {}
+    if args.dump_outputs and rank == 0:
+        model.register_forward_hook(
+            lambda _m, _inp, out: last_out.__setitem__("out", out))
+
     # ---- warmup ----
+    loss = None
     for i in range(args.warmup):
         run_step(i)
     if on_gpu:
@@ -324,7 +413,16 @@ def main():
     # ---- timed region: exactly K steps ----
     t0 = time.perf_counter()
     for i in range(args.steps):
-        run_step(args.warmup + i)
+        if init_state is not None and i == args.steps - 1:
+            # rewind outside the clock, every rank alike
+            if on_gpu:
+                torch.cuda.synchronize()
+            t_pause = time.perf_counter()
+            rewind_training_state(model, opt, init_state)
+            if on_gpu:
+                torch.cuda.synchronize()
+            t0 += time.perf_counter() - t_pause
+        loss = run_step(args.warmup + i)
     if on_gpu:
         torch.cuda.synchronize()
     if dist_ctx is not None:
@@ -340,10 +438,15 @@ def main():
     ms_per_step = elapsed / args.steps * 1000.0
     samples_per_sec = (B * world * args.steps) / elapsed
 
-    # ---- accuracy probe (outside the timed region, rank 0, 1-process GPU) --
+    # ---- what the last timed step computed (rank 0) ----
+    if args.dump_outputs and rank == 0 and loss is not None:
+        dump_outputs(args.dump_outputs, loss, model, last_out.get("out"))
+
+    # ---- accuracy probe (--full only; outside the timed region, rank 0,
+    # 1-process GPU) --
     accuracy = None
-    run_probe = args.accuracy == "on" or (
-        args.accuracy == "auto" and on_gpu and world == 1)
+    run_probe = args.full and (args.accuracy == "on" or (
+        args.accuracy == "auto" and on_gpu and world == 1))
     if run_probe and rank == 0:
         accuracy = accuracy_probe(args.accuracy_epochs, device)
 

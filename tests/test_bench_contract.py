@@ -15,6 +15,18 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _launch_env(n_ranks):
+    """Environment for an n-rank torchrun launch: RCCL refuses two ranks on
+    one device, so where fewer than n GPUs are visible the ranks run the
+    gloo CPU path, exactly as on a machine without a GPU."""
+    import torch
+
+    env = dict(os.environ)
+    if torch.cuda.is_available() and torch.cuda.device_count() < n_ranks:
+        env.update(HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    return env
+
+
 def test_bench_json_contract():
     out = subprocess.run(
         [sys.executable, "bench.py", "--steps", "2", "--warmup", "1",
@@ -53,7 +65,8 @@ def test_bench_torchrun_dp2_contract():
          "--master-port", "29537", "bench.py", "--gpus", "2",
          "--steps", "2", "--warmup", "1", "--batch", "8",
          "--endpoints", "6", "--components", "5", "--seq-len", "12"],
-        cwd=REPO, capture_output=True, text=True, timeout=420,
+        cwd=REPO, env=_launch_env(2), capture_output=True, text=True,
+        timeout=420,
     )
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
@@ -66,7 +79,8 @@ def test_bench_torchrun_dp2_contract():
 
 def test_bench_accuracy_key_default_off_on_cpu():
     """CPU default run: the accuracy key is present (contract) but null —
-    the probe only auto-runs on single-process GPU benches."""
+    the probe only runs under --full, and there only auto-runs on
+    single-process GPU benches."""
     out = subprocess.run(
         [sys.executable, "bench.py", "--steps", "1", "--warmup", "0",
          "--batch", "8", "--endpoints", "6", "--components", "5",
@@ -76,6 +90,47 @@ def test_bench_accuracy_key_default_off_on_cpu():
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert "accuracy" in d and d["accuracy"] is None
+
+
+def test_bench_dump_outputs_and_plain_run_is_lean(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float32 .npy,
+    identical inputs give matching arrays run to run, and without --full
+    the accuracy probe stays off even when --accuracy on asks for it."""
+    dumps = []
+    # CPU path on every machine: fp32 and free of atomics, so the
+    # run-to-run comparison below can be tight
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    for name in ("a", "b"):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--steps", "2", "--warmup", "1",
+             "--batch", "8", "--endpoints", "6", "--components", "5",
+             "--seq-len", "12", "--accuracy", "on",
+             "--dump-outputs", str(d)],
+            cwd=REPO, env=env, capture_output=True, text=True, timeout=600,
+        )
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(
+            [l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert line["accuracy"] is None
+        assert line["dtype"] == "fp32"
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["grads.npy", "loss.npy", "output.npy", "params.npy"]
+        dumps.append({f[:-4]: np.load(d / f) for f in files})
+    a, b = dumps
+    total = 0
+    for f, arr in a.items():
+        assert arr.dtype == np.float32 and arr.size > 0
+        assert np.isfinite(arr).all()
+        total += arr.nbytes
+        # same seeded inputs and weights -> same fp32 CPU result up to
+        # reduction order across threads
+        np.testing.assert_allclose(arr, b[f], rtol=1e-4, atol=1e-6)
+    assert total <= 64 * 1024 * 1024
+    assert a["loss"].shape == (1,)
+    assert a["params"].shape == a["grads"].shape
+    assert np.abs(a["grads"]).max() > 0
 
 
 def test_accuracy_probe_shape():
@@ -107,7 +162,8 @@ def test_bench_torchrun_dp8_contract():
          "--master-port", "29538", "bench.py", "--gpus", "8",
          "--steps", "1", "--warmup", "0", "--batch", "4",
          "--endpoints", "6", "--components", "5", "--seq-len", "12"],
-        cwd=REPO, capture_output=True, text=True, timeout=600,
+        cwd=REPO, env=_launch_env(8), capture_output=True, text=True,
+        timeout=600,
     )
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]

@@ -14,7 +14,10 @@ from deeprest_amd.ops.adam import FusedAdam
 from deeprest_amd.ops.pinball import _q_tensor
 
 
-def test_graphstep_build_returns_none_without_gpu():
+def test_graphstep_build_returns_none_without_gpu(monkeypatch):
+    # the guard under test is "no GPU visible"; make that hold on a GPU
+    # machine too
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     model = torch.nn.Linear(4, 2)
     opt = FusedAdam(model.parameters())
     x = torch.randn(3, 4)
