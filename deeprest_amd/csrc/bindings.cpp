@@ -7,6 +7,7 @@
 #include <c10/cuda/CUDAGuard.h>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <vector>
 
 // ---- C ABI launchers from the .hip translation units ----
@@ -18,6 +19,17 @@ void dr_layernorm_bwd(const void* dy, const void* x, const float* w,
                       const float* mean, const float* rstd, void* dx,
                       float* dwdb_part, int n_blocks, int64_t n_rows, int D,
                       int is_bf16, hipStream_t stream);
+void dr_dropout_add_ln_fwd(const void* branch, const void* residual, const float* w,
+                           const float* b, const int64_t* seed, uint32_t thr,
+                           float scale, void* r_out, void* normed, float* mean,
+                           float* rstd, int64_t n_rows, int D, float eps,
+                           int is_bf16, hipStream_t stream);
+void dr_dropout_add_ln_bwd(const void* d_normed, const void* d_r_out,
+                           const void* r_out, const float* w, const float* mean,
+                           const float* rstd, const int64_t* seed, uint32_t thr,
+                           float scale, void* d_res, void* d_branch,
+                           float* dwdb_part, int n_blocks, int64_t n_rows, int D,
+                           int is_bf16, hipStream_t stream);
 void dr_pinball_fwd(const void* out, const float* labels, const float* quantiles,
                     int Q, int64_t N, float inv_count, float* loss, int is_bf16,
                     hipStream_t stream);
@@ -103,6 +115,136 @@ std::vector<at::Tensor> layer_norm_backward(at::Tensor dy, at::Tensor x, at::Ten
                    cur_stream());
   auto sums = part.sum(0);  // (2, D)
   return {dx, sums[0], sums[1]};
+}
+
+// ------------------------------------------- dropout + residual + layer norm
+// seed absent: no mask (p == 0 or eval).  w/b absent: plain dropout_add.
+struct DropoutArgs {
+  const int64_t* seed = nullptr;
+  uint32_t thr = 0;
+  float scale = 1.f;
+};
+
+DropoutArgs dropout_args(const c10::optional<at::Tensor>& seed, double p,
+                         const at::Tensor& like) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0, 1), got ", p);
+  DropoutArgs a;
+  if (!seed.has_value()) return a;
+  const at::Tensor& s = *seed;
+  TORCH_CHECK(p > 0.0, "a dropout seed was given with p == 0");
+  TORCH_CHECK(s.is_cuda() && s.device() == like.device() &&
+                  s.scalar_type() == at::kLong && s.numel() == 2 &&
+                  s.is_contiguous(),
+              "dropout seed must be a contiguous int64 (key, stream) pair on ",
+              like.device());
+  a.seed = s.data_ptr<int64_t>();
+  // keep iff word >= thr, thr = min(floor(p * 2^32), 2^32 - 1), in double
+  a.thr = (uint32_t)std::min(std::floor(p * 4294967296.0), 4294967295.0);
+  a.scale = (float)(1.0 / (1.0 - p));
+  return a;
+}
+
+std::vector<at::Tensor> dropout_add_ln_forward(at::Tensor branch, at::Tensor residual,
+                                               c10::optional<at::Tensor> w,
+                                               c10::optional<at::Tensor> b,
+                                               c10::optional<at::Tensor> seed,
+                                               double p, double eps) {
+  const at::cuda::CUDAGuard guard(branch.device());
+  check_dtype(branch, "branch");
+  TORCH_CHECK(branch.is_cuda() && residual.device() == branch.device());
+  TORCH_CHECK(residual.scalar_type() == branch.scalar_type() &&
+                  residual.sizes() == branch.sizes(),
+              "branch and residual must agree in dtype and shape");
+  TORCH_CHECK(branch.is_contiguous() && residual.is_contiguous());
+  TORCH_CHECK(branch.dim() >= 1 && branch.size(-1) > 0);
+  const bool has_norm = w.has_value();
+  TORCH_CHECK(b.has_value() == has_norm, "weight and bias go together");
+  int D = (int)branch.size(-1);
+  int64_t n_rows = branch.numel() / D;
+  DropoutArgs da = dropout_args(seed, p, branch);
+  auto r_out = at::empty_like(branch);
+  auto f32 = branch.options().dtype(at::kFloat);
+  at::Tensor normed, mean, rstd;
+  if (has_norm) {
+    TORCH_CHECK(w->is_contiguous() && b->is_contiguous());
+    TORCH_CHECK(w->scalar_type() == at::kFloat && b->scalar_type() == at::kFloat,
+                "layer_norm weight/bias must be f32");
+    TORCH_CHECK(w->device() == branch.device() && b->device() == branch.device());
+    TORCH_CHECK(w->numel() == D && b->numel() == D);
+    normed = at::empty_like(branch);
+    mean = at::empty({n_rows}, f32);
+    rstd = at::empty({n_rows}, f32);
+  } else {
+    normed = at::empty({0}, branch.options());
+    mean = at::empty({0}, f32);
+    rstd = at::empty({0}, f32);
+  }
+  if (n_rows > 0)
+    dr_dropout_add_ln_fwd(branch.data_ptr(), residual.data_ptr(),
+                          has_norm ? w->data_ptr<float>() : nullptr,
+                          has_norm ? b->data_ptr<float>() : nullptr, da.seed,
+                          da.thr, da.scale, r_out.data_ptr(),
+                          has_norm ? normed.data_ptr() : nullptr,
+                          has_norm ? mean.data_ptr<float>() : nullptr,
+                          has_norm ? rstd.data_ptr<float>() : nullptr, n_rows, D,
+                          (float)eps, is_bf16(branch), cur_stream());
+  return {r_out, normed, mean, rstd};
+}
+
+// returns {d_residual, d_branch, dw, db}; without a mask d_branch IS
+// d_residual, without a norm d_residual IS d_r_out and dw/db are empty
+std::vector<at::Tensor> dropout_add_ln_backward(c10::optional<at::Tensor> d_normed,
+                                                at::Tensor d_r_out, at::Tensor r_out,
+                                                c10::optional<at::Tensor> w,
+                                                c10::optional<at::Tensor> mean,
+                                                c10::optional<at::Tensor> rstd,
+                                                c10::optional<at::Tensor> seed,
+                                                double p) {
+  const at::cuda::CUDAGuard guard(r_out.device());
+  check_dtype(r_out, "r_out");
+  TORCH_CHECK(d_r_out.is_cuda() && d_r_out.is_contiguous() && r_out.is_contiguous());
+  TORCH_CHECK(d_r_out.scalar_type() == r_out.scalar_type() &&
+              d_r_out.sizes() == r_out.sizes());
+  const bool has_norm = w.has_value();
+  TORCH_CHECK(d_normed.has_value() == has_norm && mean.has_value() == has_norm &&
+                  rstd.has_value() == has_norm,
+              "d_normed, weight, mean and rstd go together");
+  int D = (int)r_out.size(-1);
+  int64_t n_rows = r_out.numel() / D;
+  DropoutArgs da = dropout_args(seed, p, r_out);
+  const bool has_mask = da.seed != nullptr;
+  auto f32 = r_out.options().dtype(at::kFloat);
+  if (!has_norm && !has_mask) return {d_r_out, d_r_out, at::empty({0}, f32), at::empty({0}, f32)};
+  int n_blocks = (int)std::min<int64_t>((n_rows + 3) / 4, 1024);
+  if (n_blocks == 0) n_blocks = 1;
+  at::Tensor d_res = d_r_out, part;
+  if (has_norm) {
+    TORCH_CHECK(d_normed->is_contiguous() && w->is_contiguous() &&
+                mean->is_contiguous() && rstd->is_contiguous());
+    TORCH_CHECK(d_normed->scalar_type() == r_out.scalar_type() &&
+                d_normed->sizes() == r_out.sizes());
+    TORCH_CHECK(w->scalar_type() == at::kFloat && w->numel() == D);
+    TORCH_CHECK(mean->scalar_type() == at::kFloat && mean->numel() == n_rows &&
+                rstd->scalar_type() == at::kFloat && rstd->numel() == n_rows);
+    // dw/db partials live in 2 * D floats of dynamic LDS per block
+    TORCH_CHECK(D <= 8192, "dropout_add_layer_norm backward supports D <= 8192, got ", D);
+    d_res = at::empty_like(r_out);
+    part = at::zeros({n_blocks, 2, D}, f32);
+  }
+  at::Tensor d_branch = has_mask ? at::empty_like(r_out) : d_res;
+  if (n_rows > 0)
+    dr_dropout_add_ln_bwd(has_norm ? d_normed->data_ptr() : nullptr,
+                          d_r_out.data_ptr(), r_out.data_ptr(),
+                          has_norm ? w->data_ptr<float>() : nullptr,
+                          has_norm ? mean->data_ptr<float>() : nullptr,
+                          has_norm ? rstd->data_ptr<float>() : nullptr, da.seed,
+                          da.thr, da.scale, has_norm ? d_res.data_ptr() : nullptr,
+                          has_mask ? d_branch.data_ptr() : nullptr,
+                          has_norm ? part.data_ptr<float>() : nullptr, n_blocks,
+                          n_rows, D, is_bf16(r_out), cur_stream());
+  if (!has_norm) return {d_res, d_branch, at::empty({0}, f32), at::empty({0}, f32)};
+  auto sums = part.sum(0);  // (2, D)
+  return {d_res, d_branch, sums[0], sums[1]};
 }
 
 // ---------------------------------------------------------------- pinball
@@ -330,6 +472,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_featurize(m);
   m.def("layer_norm_forward", &layer_norm_forward);
   m.def("layer_norm_backward", &layer_norm_backward);
+  m.def("dropout_add_ln_forward", &dropout_add_ln_forward, py::arg("branch"),
+        py::arg("residual"), py::arg("weight"), py::arg("bias"), py::arg("seed"),
+        py::arg("p"), py::arg("eps"));
+  m.def("dropout_add_ln_backward", &dropout_add_ln_backward, py::arg("d_normed"),
+        py::arg("d_r_out"), py::arg("r_out"), py::arg("weight"), py::arg("mean"),
+        py::arg("rstd"), py::arg("seed"), py::arg("p"));
   m.def("pinball_forward", &pinball_forward);
   m.def("pinball_backward", &pinball_backward);
   m.def("fused_adam", &fused_adam);

@@ -9,28 +9,6 @@
 
 namespace dr {
 
-// ---- packed 4-column IO: one 8 B (bf16) / 16 B (f32) op per row per lane ----
-__device__ __forceinline__ void ld4(const uint16_t* p, float v[4]) {
-  uint2 u = *reinterpret_cast<const uint2*>(p);
-  v[0] = bf2f((uint16_t)(u.x & 0xffff));
-  v[1] = bf2f((uint16_t)(u.x >> 16));
-  v[2] = bf2f((uint16_t)(u.y & 0xffff));
-  v[3] = bf2f((uint16_t)(u.y >> 16));
-}
-__device__ __forceinline__ void ld4(const float* p, float v[4]) {
-  float4 u = *reinterpret_cast<const float4*>(p);
-  v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w;
-}
-__device__ __forceinline__ void st4(uint16_t* p, const float v[4]) {
-  uint2 u;
-  u.x = f2bf2(v[0], v[1]);
-  u.y = f2bf2(v[2], v[3]);
-  *reinterpret_cast<uint2*>(p) = u;
-}
-__device__ __forceinline__ void st4(float* p, const float v[4]) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-
 // Fast path for D % 4 == 0 && D <= 256 (lane owns 4 contiguous columns, the
 // whole row is one wave-wide vector op).  The column set per lane is
 // row-invariant, so w/b live in registers across the row loop.

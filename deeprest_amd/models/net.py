@@ -35,7 +35,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..data.featurize import FeaturizedData
-from ..ops import fused_gru_sequence, layer_norm, mha_forward, pinball_loss
+from ..ops import (dropout_add, dropout_add_layer_norm, fused_gru_sequence,
+                   layer_norm, mha_forward, pinball_loss)
 from ..ops.linear_bigk import bigk_linear
 
 
@@ -138,6 +139,11 @@ class DeepRestNetConfig:
                                           # ~1.1 ms/step of bias-grad
                                           # reductions at accuracy parity
                                           # (profiles/r02_perf_notes.md)
+    fused_residual_norm: bool = False     # encoder residual glue (dropout +
+                                          # add + the following LayerNorm) as
+                                          # one kernel with an in-kernel
+                                          # Philox mask; same parameters and
+                                          # state_dict keys in both modes
 
     def to_dict(self) -> dict:
         return {
@@ -147,6 +153,7 @@ class DeepRestNetConfig:
             "quantiles": tuple(self.quantiles), "dropout": self.dropout,
             "bidirectional": self.bidirectional, "prop_rounds": self.prop_rounds,
             "fp8_inference": self.fp8_inference, "linear_bias": self.linear_bias,
+            "fused_residual_norm": self.fused_residual_norm,
         }
 
 
@@ -189,6 +196,26 @@ class _EncoderLayer(nn.Module):
         h = self.ln2(x)
         x = x + self.dropout(self.ff2(F.gelu(self.ff1(h))))
         return x
+
+    def forward_fused(self, x: torch.Tensor, h: torch.Tensor,
+                      next_ln: Optional[_LayerNormOp]):
+        """Same math with the residual glue fused: takes the residual stream
+        ``x`` and ``h = ln1(x)``; the FFN residual add is fused with the NEXT
+        layer's ln1 (``next_ln``; None for the last layer).  Returns
+        ``(x, next_ln(x))`` — the second entry is None for the last layer."""
+        B, T, D = x.shape
+        p, training = self.dropout.p, self.training
+        qkv = self.qkv(h).view(B, T, 3, self.n_heads, D // self.n_heads)
+        q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # (B,h,T,dh)
+        attn = mha_forward(q, k, v)
+        attn = attn.transpose(1, 2).reshape(B, T, D)
+        x, h = dropout_add_layer_norm(self.proj(attn), x, self.ln2.weight,
+                                      self.ln2.bias, p, training, self.ln2.eps)
+        ff = self.ff2(F.gelu(self.ff1(h)))
+        if next_ln is None:
+            return dropout_add(ff, x, p, training), None
+        return dropout_add_layer_norm(ff, x, next_ln.weight, next_ln.bias, p,
+                                      training, next_ln.eps)
 
 
 class _GraphPropagation(nn.Module):
@@ -340,13 +367,31 @@ class DeepRestNet(nn.Module):
         x = self.in_proj(traffic)
         x = x + self._pos_encoding(T, x.device, x.dtype)
         x = self.in_norm(x)
-        for layer in self.layers:
-            x = layer(x)
+        if self.cfg.fused_residual_norm:
+            x = self._encode_fused(x)
+        else:
+            for layer in self.layers:
+                x = layer(x)
         comp = self.graph()                                   # (C, comp_dim)
         fp8 = (self.cfg.fp8_inference and not self.training
                and traffic.is_cuda and not torch.is_grad_enabled())
         h_dirs = self.decoder(x, comp, fp8=fp8)               # tuple of (B,T,C,H)
         return self._apply_heads(h_dirs)
+
+    def _encode_fused(self, x: torch.Tensor) -> torch.Tensor:
+        """Encoder stack with cfg.fused_residual_norm: carries the residual
+        stream ``x`` and the normed tensor ``h`` the next sub-block consumes,
+        so every ``x + dropout(branch)`` and the LayerNorm after it are one
+        kernel.  Layer 0's ln1 has no residual add in front of it and is the
+        plain layer_norm; the last FFN add has no LayerNorm behind it."""
+        n = len(self.layers)
+        if n == 0:
+            return x
+        h = self.layers[0].ln1(x)
+        for i, layer in enumerate(self.layers):
+            next_ln = self.layers[i + 1].ln1 if i + 1 < n else None
+            x, h = layer.forward_fused(x, h, next_ln)
+        return x
 
     def _apply_heads(self, h_dirs) -> torch.Tensor:
         """Per-resource heads as a sum of per-direction GEMMs (no concat),
@@ -400,6 +445,8 @@ class DeepRestNet(nn.Module):
             x = self.in_proj(x)
             x = x + self._pos_encoding(x.shape[1], x.device, x.dtype)
             x = self.in_norm(x)
+            if cfg.fused_residual_norm:
+                return self._encode_fused(x)
             for layer in self.layers:
                 x = layer(x)
             return x

@@ -15,6 +15,8 @@ can never masquerade as kernel coverage.
 from .native import native_available, require_native, load_native
 from .gru import fused_gru_sequence, reference_gru_sequence
 from .layernorm import layer_norm, reference_layer_norm
+from .residual_norm import (dropout_add, dropout_add_layer_norm, philox_keep_mask,
+                            reference_dropout_add_layer_norm)
 from .attention import mha_forward, reference_mha
 from .pinball import pinball_loss, reference_pinball_loss
 from .adam import fused_adam_step
@@ -27,6 +29,10 @@ __all__ = [
     "reference_gru_sequence",
     "layer_norm",
     "reference_layer_norm",
+    "dropout_add",
+    "dropout_add_layer_norm",
+    "philox_keep_mask",
+    "reference_dropout_add_layer_norm",
     "mha_forward",
     "reference_mha",
     "pinball_loss",
