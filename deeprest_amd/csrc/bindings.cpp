@@ -47,11 +47,12 @@ void dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
                 const void* w_hh, const float* b_hh, const void* h0, void* h_all,
                 void* saves, int B, int TT, int C, int reverse, int save,
                 int fp8, int is_bf16, hipStream_t stream);
-void dr_gru_bwd(const void* grad_h, const void* w_img, const void* w_fwd,
-                const void* xg, const void* gamma, const void* beta,
-                const float* b_hh, const void* h0, const void* h_all,
-                const void* saves, void* dpre, float* dh0, int B, int TT, int C,
-                int reverse, int is_bf16, hipStream_t stream);
+void dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
+                const void* w_fwd, const void* xg, const void* gamma,
+                const void* beta, const float* b_hh, const void* h0,
+                const void* h_all, const void* saves, void* dpre, float* dh0,
+                int B, int TT, int C, int reverse, int is_bf16,
+                hipStream_t stream);
 void dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
                        void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
                        void* xg_pi, int64_t BT, int C, int is_bf16,
@@ -371,16 +372,43 @@ std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
   return {h_all, saves};
 }
 
-std::vector<at::Tensor> gru_seq_backward_kernel(at::Tensor grad_h, at::Tensor w_img,
-                                                at::Tensor w_fwd, at::Tensor xg,
-                                                at::Tensor gamma, at::Tensor beta,
-                                                at::Tensor b_hh, at::Tensor h0,
-                                                at::Tensor h_all, at::Tensor saves,
-                                                bool reverse) {
+// Sequential backward chain.  wh_img == nullptr: grad is grad_h (B, T, C, H).
+// Otherwise grad is the quantile heads' output gradient (B, T, C, O) and the
+// kernel forms grad @ w_head per step from the (H, 32) weight image.
+static std::vector<at::Tensor> gru_backward_impl(
+    at::Tensor grad_h, const at::Tensor* wh_img, at::Tensor w_img,
+    at::Tensor w_fwd, at::Tensor xg, at::Tensor gamma, at::Tensor beta,
+    at::Tensor b_hh, at::Tensor h0, at::Tensor h_all, at::Tensor saves,
+    bool reverse) {
   const at::cuda::CUDAGuard guard(grad_h.device());
-  int B = (int)grad_h.size(0), TT = (int)grad_h.size(1);
-  int C = (int)grad_h.size(2), H = (int)grad_h.size(3);
+  TORCH_CHECK(grad_h.dim() == 4 && h_all.dim() == 4, "grad and h_all must be 4-D");
+  int B = (int)h_all.size(0), TT = (int)h_all.size(1);
+  int C = (int)h_all.size(2), H = (int)h_all.size(3);
   TORCH_CHECK(H == 128);
+  TORCH_CHECK(grad_h.size(0) == B && grad_h.size(1) == TT && grad_h.size(2) == C,
+              "gru backward: grad leading dims must match h_all (B, T, C)");
+  int O = 0;
+  if (wh_img != nullptr) {
+    O = (int)grad_h.size(3);
+    TORCH_CHECK(O >= 1 && O <= 32, "fused head gradient needs 1 <= O <= 32, got ", O);
+    TORCH_CHECK(wh_img->scalar_type() == at::kBFloat16 &&
+                    wh_img->sizes() == at::IntArrayRef({H, 32}) &&
+                    wh_img->is_contiguous() && wh_img->is_cuda(),
+                "wh_img must be the (H, 32) bf16 head weight image");
+  } else {
+    TORCH_CHECK(grad_h.size(3) == H, "grad_h must be (B, T, C, H)");
+  }
+  TORCH_CHECK(xg.sizes() == at::IntArrayRef({B, TT, 3 * H}) &&
+                  h0.sizes() == at::IntArrayRef({B, C, H}) &&
+                  gamma.sizes() == at::IntArrayRef({C, 3 * H}) &&
+                  beta.sizes() == at::IntArrayRef({C, 3 * H}) &&
+                  b_hh.numel() == 3 * H,
+              "gru backward: operand shapes do not match h_all");
+  TORCH_CHECK(xg.is_contiguous() && h0.is_contiguous() && gamma.is_contiguous() &&
+              beta.is_contiguous());
+  TORCH_CHECK(h_all.scalar_type() == grad_h.scalar_type() &&
+              saves.scalar_type() == grad_h.scalar_type() &&
+              h0.scalar_type() == grad_h.scalar_type());
   TORCH_CHECK(saves.numel() == (int64_t)B * TT * C * 2 * H,
               "gru backward: saves tensor missing or wrong size (forward must "
               "run with save=true)");
@@ -399,12 +427,33 @@ std::vector<at::Tensor> gru_seq_backward_kernel(at::Tensor grad_h, at::Tensor w_
   TORCH_CHECK(grad_h.is_contiguous() && h_all.is_contiguous() && saves.is_contiguous());
   auto dpre = at::empty({B, TT, C, 4 * H}, grad_h.options());
   auto dh0 = at::empty({B, C, H}, grad_h.options().dtype(at::kFloat));
-  dr_gru_bwd(grad_h.data_ptr(), w_img.data_ptr(), w_fwd.data_ptr(), xg.data_ptr(),
+  dr_gru_bwd(grad_h.data_ptr(), wh_img ? wh_img->data_ptr() : nullptr, O,
+             w_img.data_ptr(), w_fwd.data_ptr(), xg.data_ptr(),
              gamma.data_ptr(), beta.data_ptr(), b_hh.data_ptr<float>(),
              h0.data_ptr(), h_all.data_ptr(), saves.data_ptr(), dpre.data_ptr(),
              dh0.data_ptr<float>(), B, TT, C, reverse ? 1 : 0,
              dt == at::kBFloat16, cur_stream());
   return {dpre, dh0};
+}
+
+std::vector<at::Tensor> gru_seq_backward_kernel(at::Tensor grad_h, at::Tensor w_img,
+                                                at::Tensor w_fwd, at::Tensor xg,
+                                                at::Tensor gamma, at::Tensor beta,
+                                                at::Tensor b_hh, at::Tensor h0,
+                                                at::Tensor h_all, at::Tensor saves,
+                                                bool reverse) {
+  return gru_backward_impl(grad_h, nullptr, w_img, w_fwd, xg, gamma, beta, b_hh,
+                           h0, h_all, saves, reverse);
+}
+
+// grad_part: (B, T, C, O) head output gradient, O <= 32; wh_img: (H, 32) bf16
+// with wh_img[n][k] = w_head[k][n] and zeros for k >= O
+std::vector<at::Tensor> gru_seq_backward_heads_kernel(
+    at::Tensor grad_part, at::Tensor wh_img, at::Tensor w_img, at::Tensor w_fwd,
+    at::Tensor xg, at::Tensor gamma, at::Tensor beta, at::Tensor b_hh,
+    at::Tensor h0, at::Tensor h_all, at::Tensor saves, bool reverse) {
+  return gru_backward_impl(grad_part, &wh_img, w_img, w_fwd, xg, gamma, beta,
+                           b_hh, h0, h_all, saves, reverse);
 }
 
 // single-pass reductions over dpre: dxg, dgamma, dbeta
@@ -486,6 +535,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("b_hh"), py::arg("h0"), py::arg("gamma"), py::arg("beta"),
         py::arg("reverse"), py::arg("save"), py::arg("fp8") = false);
   m.def("gru_seq_backward_kernel", &gru_seq_backward_kernel);
+  m.def("gru_seq_backward_heads_kernel", &gru_seq_backward_heads_kernel);
   m.def("gru_bwd_reduce", &gru_bwd_reduce);
   m.def("mha_forward", &mha_forward);
   m.def("mha_backward", &mha_backward);

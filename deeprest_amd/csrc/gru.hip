@@ -492,9 +492,16 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
 // NSUB = 2: 8 waves / 128 rows, the pi-permuted W image staged ONCE in LDS
 //           (96 KB) — 2 waves/SIMD from one block with low-latency
 //           B-fragments; used when the grid still fills the chip.
-template <typename T, int NSUB>
+// FUSED: the upstream gradient arrives as the quantile heads' narrow output
+//        gradient grad_part (B, TT, C, O), O <= 32, instead of grad_h.  Per
+//        step one K=32 MFMA per 16-column tile forms grad_part @ w_head
+//        straight into the dh_carry accumulators (same C-fragment layout),
+//        so the (B, TT, C, H) head input gradient is never materialized.
+template <typename T, int NSUB, bool FUSED>
 __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
-    const T* __restrict__ grad_h,   // (B, TT, C, H)
+    const T* __restrict__ grad_h,   // (B, TT, C, H); FUSED: grad_part (B, TT, C, O)
+    const uint16_t* __restrict__ wh_img,  // FUSED: (H, 32) bf16, wh_img[n][k] =
+                                          // w_head[k][n], zero for k >= O
     const uint16_t* __restrict__ w_img,  // (H, 384) bf16: w_img[k][m] = W[natJ(m)][k]
     const uint16_t* __restrict__ w_fwd,  // (3H, H) bf16 natural layout
     const T* __restrict__ xg,       // (B, TT, 3H)
@@ -506,9 +513,10 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
     const T* __restrict__ saves,    // (B, TT, C, 2H) pi layout: r|z
     T* __restrict__ dpre,           // (B, TT, C, 4H) pi: dr|dz|dn|d_hhn
     float* __restrict__ dh0,        // (B, C, H)
-    int B, int TT, int C, int reverse) {
+    int B, int TT, int C, int reverse, int O) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* wn_lds = smem + H * G3H * 2;   // (NSUB==2) 128 x 128 bf16 swizzled
+  char* wh_lds = wn_lds + H * H * 2;   // (NSUB==2, FUSED) 128 x 32 bf16 linear
   const int tid = threadIdx.x;
   const int wv = tid / DR_WAVE;
   const int lane = tid % DR_WAVE;
@@ -531,6 +539,13 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
           w_fwd + (int64_t)(2 * H + jl) * H + blk * 8);
       *reinterpret_cast<bf16x8*>(wn_lds + jl * 256 + ((blk ^ (jl & 15)) << 4)) = v;
     }
+    // head weight image (8 KB), linear [n][32]: a wave's 64 fragment reads
+    // per N-tile cover 1 KB contiguous, so no swizzle is needed
+    if constexpr (FUSED) {
+      for (int id = tid; id < H * 4; id += NSUB * THREADS)
+        *reinterpret_cast<bf16x8*>(wh_lds + id * 16) =
+            *reinterpret_cast<const bf16x8*>(wh_img + id * 8);
+    }
   }
 
   const int c_col = lane & 15;
@@ -549,11 +564,15 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
     comp_of[i] = (int)(rr % C);
   }
 
-  float dh_carry[4][8];
+  // dh carry in MFMA C-fragment order: dh_carry[nt][i] <-> (row rgrp*4+i,
+  // col nt*16+c_col).  Kept as scalars (an f32x4 array pinned the unfused
+  // variants to register quads: +11 VGPRs, scratch on the fp32 one); the
+  // FUSED head MFMA gathers/scatters one tile's four values around itself.
+  float dh_carry[8][4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int nt = 0; nt < 8; ++nt)
 #pragma unroll
-    for (int nt = 0; nt < 8; ++nt) dh_carry[i][nt] = 0.f;
+    for (int i = 0; i < 4; ++i) dh_carry[nt][i] = 0.f;
   if constexpr (NSUB == 2) __syncthreads();  // W staging visible to all waves
 
   // ---- compact addressing: per-row indices + ONE shared per-step offset ----
@@ -591,6 +610,40 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
     // h_all of the step before; h0 is the prev only at the LAST processed
     // step (= forward t boundary)
     const bool use_h0 = (step == TT - 1);
+
+    if constexpr (FUSED) {
+      // ---- dh_carry += grad_part[rows, :O] @ w_head (one K=32 MFMA/tile) ----
+      // A-fragment: lane (arow, k0) holds grad_part[arow, k0..k0+7].  The
+      // address is clamped into the row and k >= O is forced to exact zero
+      // (select, not a branch: every lane issues the same 8 loads).
+      const T* gp = grad_h + (abc0 + bc_toff) * O;
+      uint16_t av[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = k0 + j;
+        const T raw = gp[k < O ? k : O - 1];
+        uint16_t b;
+        if constexpr (sizeof(T) == 2) b = (uint16_t)raw; else b = f2bf(raw);
+        av[j] = (k < O) ? b : (uint16_t)0;
+      }
+      const bf16x8 afrag = *reinterpret_cast<const bf16x8*>(av);
+      const uint16_t* whv = wh_img;
+      if constexpr (NSUB == 1) asm volatile("" : "+v"(whv));
+#pragma unroll
+      for (int nt = 0; nt < 8; ++nt) {
+        const int n = nt * 16 + c_col;
+        bf16x8 bfrag;
+        if constexpr (NSUB == 2)
+          bfrag = lds_read8(wh_lds, n * 64 + k0 * 2);
+        else
+          bfrag = *reinterpret_cast<const bf16x8*>(whv + n * 32 + k0);
+        f32x4 c = {dh_carry[nt][0], dh_carry[nt][1], dh_carry[nt][2],
+                   dh_carry[nt][3]};
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, bfrag, c, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dh_carry[nt][i] = c[i];
+      }
+    }
 
     // ---- recompute hh_n = h_prev @ W_hn^T for this wave's 16 rows ----
     // (saving it cost 2H of HBM each way; one extra HxH MFMA pass is cheaper)
@@ -638,7 +691,7 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
       // pointer select -> ONE load (the OOB address is never dereferenced)
       const T* hsrc = use_h0 ? (h0 + h0_off[i])
                              : (h_all + (bc + dirC) * H);
-      const T* gr_p = grad_h + bc * H;
+      const T* gr_p = grad_h + bc * H;   // !FUSED only
       const T* xg_n = xg + xgb0[i] + xg_toff + 2 * H;
       const T* gmn = gm_v + comp_of[i] * G3H + 2 * H;
       const T* btn = bt_v + comp_of[i] * G3H + 2 * H;
@@ -646,12 +699,12 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
       for (int nt = 0; nt < 8; ++nt) {
         int col = nt * 16 + c_col;
         float hp = ldf(hsrc + col);
-        float g = ldf(gr_p + col);
         // recompute the n gate: hh_n from the GEMM above, g_n from xg/FiLM
         float hn = hhn_acc[nt][i] + bhn[nt];
         float g_n = ldf(xg_n + col) * ldf(gmn + col) + ldf(btn + col);
         float nn = tanhf_(g_n + rp[nt] * hn);
-        float dht = g + dh_carry[i][nt];
+        float dht = dh_carry[nt][i];       // FUSED: head term already in
+        if constexpr (!FUSED) dht += ldf(gr_p + col);
         float dz = dht * (hp - nn);
         float dn = dht * (1.f - zp[nt]);
         float dnp = dn * (1.f - nn * nn);
@@ -661,7 +714,7 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
         fdz[nt] = dz * zp[nt] * (1.f - zp[nt]);
         fdn[nt] = dnp;
         fdh[nt] = dhhn;
-        dh_carry[i][nt] = dht * zp[nt];    // partial; MFMA adds dpre @ W
+        dh_carry[nt][i] = dht * zp[nt];    // partial; MFMA adds dpre @ W
       }
       T* dx_p = dpre + bc * G4H + c_col * 8;
       st8(dx_p, fdr);
@@ -709,7 +762,7 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
           a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[kt], bfrag, a, 0, 0, 0);
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dh_carry[i][nt] += a[i];
+        for (int i = 0; i < 4; ++i) dh_carry[nt][i] += a[i];
       }
     }
     bc_toff += dirC;
@@ -725,7 +778,7 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (!live[i]) continue;
-      dh0[((int64_t)b_of[i] * C + comp_of[i]) * H + col] = dh_carry[i][nt];
+      dh0[((int64_t)b_of[i] * C + comp_of[i]) * H + col] = dh_carry[nt][i];
     }
   }
 }
@@ -941,38 +994,42 @@ static void gru_fwd_launch_t(const void* xg, const void* gamma, const void* beta
                        (T*)h_all, (T*)saves, B, TT, C, reverse);
 }
 
-template <typename T>
-static void gru_bwd_launch_t(const void* grad_h, const void* w_img,
-                             const void* w_fwd, const void* xg, const void* gamma,
-                             const void* beta, const float* b_hh, const void* h0,
+template <typename T, bool FUSED>
+static void gru_bwd_launch_t(const void* grad_h, const void* wh_img,
+                             const void* w_img, const void* w_fwd, const void* xg,
+                             const void* gamma, const void* beta,
+                             const float* b_hh, const void* h0,
                              const void* h_all, const void* saves, void* dpre,
-                             float* dh0, int B, int TT, int C, int reverse,
+                             float* dh0, int B, int TT, int C, int reverse, int O,
                              hipStream_t stream) {
   int64_t R = (int64_t)B * C;
   int tiles128 = (int)((R + 2 * ROWS - 1) / (2 * ROWS));
   if (tiles128 >= 192) {
     // enough 128-row tiles to fill the chip at 1 block/CU: LDS-W variant
-    constexpr int LDS_WB = H * G3H * 2 + H * H * 2;  // 96 + 32 KB
+    // 96 KB W image + 32 KB W_hn (+ 8 KB head weight image when FUSED)
+    constexpr int LDS_WB = H * G3H * 2 + H * H * 2 + (FUSED ? H * 32 * 2 : 0);
     static bool attr_set = false;
     if (!attr_set) {
       DR_HIP_CHECK(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&gru_bwd_kernel<T, 2>),
+          reinterpret_cast<const void*>(&gru_bwd_kernel<T, 2, FUSED>),
           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WB));
       attr_set = true;
     }
-    hipLaunchKernelGGL((gru_bwd_kernel<T, 2>), dim3(tiles128), dim3(2 * THREADS),
-                       LDS_WB, stream, (const T*)grad_h, (const uint16_t*)w_img,
+    hipLaunchKernelGGL((gru_bwd_kernel<T, 2, FUSED>), dim3(tiles128),
+                       dim3(2 * THREADS), LDS_WB, stream, (const T*)grad_h,
+                       (const uint16_t*)wh_img, (const uint16_t*)w_img,
                        (const uint16_t*)w_fwd, (const T*)xg, (const T*)gamma,
                        (const T*)beta, b_hh, (const T*)h0, (const T*)h_all,
-                       (const T*)saves, (T*)dpre, dh0, B, TT, C, reverse);
+                       (const T*)saves, (T*)dpre, dh0, B, TT, C, reverse, O);
     return;
   }
   int grid = (int)((R + ROWS - 1) / ROWS);
-  hipLaunchKernelGGL((gru_bwd_kernel<T, 1>), dim3(grid), dim3(THREADS), 0, stream,
-                     (const T*)grad_h, (const uint16_t*)w_img,
-                     (const uint16_t*)w_fwd, (const T*)xg, (const T*)gamma,
-                     (const T*)beta, b_hh, (const T*)h0, (const T*)h_all,
-                     (const T*)saves, (T*)dpre, dh0, B, TT, C, reverse);
+  hipLaunchKernelGGL((gru_bwd_kernel<T, 1, FUSED>), dim3(grid), dim3(THREADS), 0,
+                     stream, (const T*)grad_h, (const uint16_t*)wh_img,
+                     (const uint16_t*)w_img, (const uint16_t*)w_fwd,
+                     (const T*)xg, (const T*)gamma, (const T*)beta, b_hh,
+                     (const T*)h0, (const T*)h_all, (const T*)saves, (T*)dpre,
+                     dh0, B, TT, C, reverse, O);
 }
 
 template <typename T>
@@ -1025,19 +1082,34 @@ void dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
                                 B, TT, C, reverse, save, fp8, stream);
 }
 
-void dr_gru_bwd(const void* grad_h, const void* w_img, const void* w_fwd,
-                const void* xg, const void* gamma, const void* beta,
-                const float* b_hh, const void* h0, const void* h_all,
-                const void* saves, void* dpre, float* dh0, int B, int TT, int C,
-                int reverse, int is_bf16, hipStream_t stream) {
+// wh_img == nullptr: grad is grad_h (B, TT, C, H), the unfused path.
+// Otherwise grad is the heads' grad_part (B, TT, C, O) and wh_img the (H, 32)
+// bf16 zero-padded transposed head weight image.
+void dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
+                const void* w_fwd, const void* xg, const void* gamma,
+                const void* beta, const float* b_hh, const void* h0,
+                const void* h_all, const void* saves, void* dpre, float* dh0,
+                int B, int TT, int C, int reverse, int is_bf16,
+                hipStream_t stream) {
+  if (wh_img != nullptr) {
+    if (is_bf16)
+      dr::gru_bwd_launch_t<uint16_t, true>(grad, wh_img, w_img, w_fwd, xg, gamma,
+                                           beta, b_hh, h0, h_all, saves, dpre,
+                                           dh0, B, TT, C, reverse, O, stream);
+    else
+      dr::gru_bwd_launch_t<float, true>(grad, wh_img, w_img, w_fwd, xg, gamma,
+                                        beta, b_hh, h0, h_all, saves, dpre, dh0,
+                                        B, TT, C, reverse, O, stream);
+    return;
+  }
   if (is_bf16)
-    dr::gru_bwd_launch_t<uint16_t>(grad_h, w_img, w_fwd, xg, gamma, beta, b_hh,
-                                   h0, h_all, saves, dpre, dh0, B, TT, C,
-                                   reverse, stream);
+    dr::gru_bwd_launch_t<uint16_t, false>(grad, nullptr, w_img, w_fwd, xg, gamma,
+                                          beta, b_hh, h0, h_all, saves, dpre,
+                                          dh0, B, TT, C, reverse, 0, stream);
   else
-    dr::gru_bwd_launch_t<float>(grad_h, w_img, w_fwd, xg, gamma, beta, b_hh,
-                                h0, h_all, saves, dpre, dh0, B, TT, C,
-                                reverse, stream);
+    dr::gru_bwd_launch_t<float, false>(grad, nullptr, w_img, w_fwd, xg, gamma,
+                                       beta, b_hh, h0, h_all, saves, dpre, dh0,
+                                       B, TT, C, reverse, 0, stream);
 }
 
 void dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,

@@ -35,8 +35,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..data.featurize import FeaturizedData
-from ..ops import (dropout_add, dropout_add_layer_norm, fused_gru_sequence,
-                   layer_norm, mha_forward, pinball_loss)
+from ..ops import (dropout_add, dropout_add_layer_norm, fused_gru_heads,
+                   fused_gru_sequence, layer_norm, mha_forward, pinball_loss)
+from ..ops.gru import HEAD_FUSE_MAX_OUT, gru_kernel_supports
 from ..ops.linear_bigk import bigk_linear
 
 
@@ -144,6 +145,15 @@ class DeepRestNetConfig:
                                           # one kernel with an in-kernel
                                           # Philox mask; same parameters and
                                           # state_dict keys in both modes
+    fused_head_grad: bool = True          # decoder + quantile heads as one
+                                          # autograd node per direction: the
+                                          # GRU backward kernel forms the head
+                                          # input gradient from the Q-wide head
+                                          # gradient itself (no (B,T,C,H)
+                                          # round trip); applies when the
+                                          # native GRU kernel runs and head
+                                          # dropout is inactive; same
+                                          # parameters and state_dict keys
 
     def to_dict(self) -> dict:
         return {
@@ -154,6 +164,7 @@ class DeepRestNetConfig:
             "bidirectional": self.bidirectional, "prop_rounds": self.prop_rounds,
             "fp8_inference": self.fp8_inference, "linear_bias": self.linear_bias,
             "fused_residual_norm": self.fused_residual_norm,
+            "fused_head_grad": self.fused_head_grad,
         }
 
 
@@ -304,6 +315,28 @@ class _GRUDecoderBank(nn.Module):
                                    gamma_r, beta_r, reverse=True, fp8=fp8)
         return (out, out_r)
 
+    def forward_heads(self, enc: torch.Tensor, comp: torch.Tensor,
+                      w_heads: Sequence[torch.Tensor]) -> torch.Tensor:
+        """Decoder and head projection as one op per direction
+        (ops.fused_gru_heads): ``w_heads[d]`` is direction d's (O, H) head
+        weight slice; returns the summed head output (B, T, C, O).  Same
+        math as ``forward`` followed by a per-direction linear."""
+        B = enc.shape[0]
+        C = comp.shape[0]
+        out = None
+        for d in range(2 if self.bidirectional else 1):
+            sfx = "_r" if d else ""
+            xg = getattr(self, "x_proj" + sfx)(enc)            # (B, T, 3H)
+            gamma = getattr(self, "cond_gamma" + sfx)(comp)    # (C, 3H)
+            beta = getattr(self, "cond_beta" + sfx)(comp)
+            h0 = torch.tanh(getattr(self, "h0_proj" + sfx)(comp))
+            h0 = h0.unsqueeze(0).expand(B, C, self.hidden).contiguous()
+            part = fused_gru_heads(xg, getattr(self, "w_hh" + sfx),
+                                   getattr(self, "b_hh" + sfx), h0, gamma, beta,
+                                   w_heads[d], reverse=bool(d))
+            out = part if out is None else out + part
+        return out
+
 
 # -------------------------------------------------------------------- model
 class DeepRestNet(nn.Module):
@@ -375,8 +408,28 @@ class DeepRestNet(nn.Module):
         comp = self.graph()                                   # (C, comp_dim)
         fp8 = (self.cfg.fp8_inference and not self.training
                and traffic.is_cuda and not torch.is_grad_enabled())
+        if self._use_fused_heads(x, comp, fp8):
+            H = self.cfg.hidden
+            w_all = self._head_weights()
+            dirs = 2 if self.cfg.bidirectional else 1
+            w_dirs = [w_all[:, d * H : (d + 1) * H].contiguous()
+                      for d in range(dirs)]
+            return self._finish_heads(self.decoder.forward_heads(x, comp, w_dirs))
         h_dirs = self.decoder(x, comp, fp8=fp8)               # tuple of (B,T,C,H)
         return self._apply_heads(h_dirs)
+
+    def _use_fused_heads(self, enc: torch.Tensor, comp: torch.Tensor,
+                         fp8: bool) -> bool:
+        """cfg.fused_head_grad applies when the decoder runs the native GRU
+        kernel (not its fp8 inference variant), the head dropout is the
+        identity, and all heads together fit one K=32 MFMA step."""
+        if not self.cfg.fused_head_grad or fp8 or not enc.is_cuda:
+            return False
+        if not gru_kernel_supports(self.cfg.hidden, comp.shape[0]):
+            return False
+        if self.training and self.dropout.p > 0:
+            return False
+        return len(self.heads) * len(self.cfg.quantiles) <= HEAD_FUSE_MAX_OUT
 
     def _encode_fused(self, x: torch.Tensor) -> torch.Tensor:
         """Encoder stack with cfg.fused_residual_norm: carries the residual
@@ -397,13 +450,20 @@ class DeepRestNet(nn.Module):
         """Per-resource heads as a sum of per-direction GEMMs (no concat),
         each with a batched-K backward (ops/linear_bigk.py)."""
         H = self.cfg.hidden
-        w_all = torch.cat([h.weight for h in self.heads], dim=0)   # (R*Q, H*dirs)
+        w_all = self._head_weights()
         out = None
         for d, h_d in enumerate(h_dirs):
             h_d = self.dropout(h_d)
             part = bigk_linear(h_d, w_all[:, d * H : (d + 1) * H].contiguous())
             out = part if out is None else out + part
-        B, T, C = h_dirs[0].shape[0], h_dirs[0].shape[1], h_dirs[0].shape[2]
+        return self._finish_heads(out)
+
+    def _head_weights(self) -> torch.Tensor:
+        return torch.cat([h.weight for h in self.heads], dim=0)    # (R*Q, H*dirs)
+
+    def _finish_heads(self, out: torch.Tensor) -> torch.Tensor:
+        """(B, T, C, R*Q) summed head outputs -> (B, T, M, Q) predictions."""
+        B, T, C = out.shape[0], out.shape[1], out.shape[2]
         R = len(self.heads)
         Q = len(self.cfg.quantiles)
         outs = out.view(B, T, C, R, Q)

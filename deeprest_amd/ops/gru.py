@@ -113,68 +113,129 @@ class _FusedGRUSequence(torch.autograd.Function):
         ext = require_native("fused_gru_sequence")
         x_gates, w_hh, b_hh, h0, gamma, beta, h_all, saves = ctx.saved_tensors
         reverse = ctx.reverse
-        # pi-permuted W image (H, 3H) for the dh GEMM: row k holds
-        # W[natJ(m), k] over the MFMA K axis m (dr | dz | d_hhn regions).
-        # Cast once, then gather/transpose in bf16 (fewer/smaller copies).
-        natj, _ = _pi_indices(w_hh.device)
-        w_fwd = w_hh.to(torch.bfloat16).contiguous()  # hh_n recompute GEMM
-        w_img = w_fwd[natj, :].t().contiguous()
+        w_img, w_fwd = _bwd_weight_images(w_hh)
         # sequential chain (custom kernel): dpre = [dr_pre|dz_pre|dn_pre|d_hh_n]
         dpre, dh0 = ext.gru_seq_backward_kernel(
             grad_h_all.contiguous(), w_img, w_fwd, x_gates, gamma, beta, b_hh,
             h0, h_all, saves, reverse
         )
-        B, T, C, G4 = dpre.shape
-        H = G4 // 4
+        return _bwd_reductions(ext, dpre, dh0, x_gates, w_hh, h0, gamma, h_all,
+                               reverse) + (None,)
 
-        # dpre rows use the kernel's pi packing: position g*128 + cc*8 + nt
-        # holds natural column g*128 + nt*16 + cc — unpermute dW rows after
-        # the GEMM (tiny index_copy on a (K, H) matrix).
-        _, nat4 = _pi_indices(w_hh.device)
 
-        def unpi(dw_pi):
-            out = torch.empty_like(dw_pi)
-            out.index_copy_(0, nat4[: dw_pi.shape[0]], dw_pi)
-            return out
+def _bwd_weight_images(w_hh):
+    """bf16 weight images the backward kernel reads: the pi-permuted W image
+    (H, 3H) for the dh GEMM — row k holds W[natJ(m), k] over the MFMA K axis
+    m (dr | dz | d_hhn regions) — and the natural (3H, H) image for the hh_n
+    recompute GEMM.  Cast once, then gather/transpose in bf16 (fewer/smaller
+    copies)."""
+    natj, _ = _pi_indices(w_hh.device)
+    w_fwd = w_hh.to(torch.bfloat16).contiguous()
+    w_img = w_fwd[natj, :].t().contiguous()
+    return w_img, w_fwd
 
-        # dW_hh = sum over (b,t,c) of [dr|dz|d_hhn]^T h_prev — batched strided
-        # GEMMs (rocBLAS picks per-B batching => proper chip occupancy; no cats:
-        # the t=0/t=T-1 boundary term against h0 is a separate small bmm)
-        def dw_for(cols):
-            if reverse:
-                dp_main = dpre[:, :-1, :, cols]             # h_prev = h_all[t+1]
-                h_main = h_all[:, 1:]
-                dp_bound = dpre[:, -1, :, cols]             # h_prev = h0
-            else:
-                dp_main = dpre[:, 1:, :, cols]              # h_prev = h_all[t-1]
-                h_main = h_all[:, :-1]
-                dp_bound = dpre[:, 0, :, cols]
-            K = dp_main.shape[-1]
-            a = dp_main.reshape(B, (T - 1) * C, K).transpose(1, 2)
-            part = torch.bmm(a, h_main.reshape(B, (T - 1) * C, H))
-            ab = dp_bound.reshape(B, C, K).transpose(1, 2)
-            part = part + torch.bmm(ab, h0)
-            return unpi(part.sum(0, dtype=torch.float32))   # (K, H) natural rows
 
-        dw_rz = dw_for(slice(0, 2 * H))
-        dw_n = dw_for(slice(3 * H, 4 * H))
-        dw_hh = torch.cat([dw_rz, dw_n], dim=0)             # (3H, H) f32
+def _bwd_reductions(ext, dpre, dh0, x_gates, w_hh, h0, gamma, h_all, reverse):
+    """Everything after the sequential chain, shared by the plain and the
+    head-fused backward: returns (dxg, dw_hh, db_hh, dh0, dgamma, dbeta)."""
+    B, T, C, G4 = dpre.shape
+    H = G4 // 4
 
-        # single-pass fused reductions (custom kernel): dxg, dgamma, dbeta4
-        # (dbeta4's 4th slice is sum of d_hh_n -> the n-part of db_hh)
-        dxg, dgamma, dbeta4 = ext.gru_bwd_reduce(dpre, gamma, x_gates)
-        s4 = dbeta4.sum(dim=0)                              # (4H,) f32, tiny
-        db_hh = torch.cat([s4[: 2 * H], s4[3 * H :]])
-        dbeta = dbeta4[:, : 3 * H]
-        return (
-            dxg,
-            dw_hh.to(w_hh.dtype),
-            db_hh,
-            dh0.to(h0.dtype),
-            dgamma.to(gamma.dtype),
-            dbeta.to(gamma.dtype),
-            None,
+    # dpre rows use the kernel's pi packing: position g*128 + cc*8 + nt
+    # holds natural column g*128 + nt*16 + cc — unpermute dW rows after
+    # the GEMM (tiny index_copy on a (K, H) matrix).
+    _, nat4 = _pi_indices(w_hh.device)
+
+    def unpi(dw_pi):
+        out = torch.empty_like(dw_pi)
+        out.index_copy_(0, nat4[: dw_pi.shape[0]], dw_pi)
+        return out
+
+    # dW_hh = sum over (b,t,c) of [dr|dz|d_hhn]^T h_prev — batched strided
+    # GEMMs (rocBLAS picks per-B batching => proper chip occupancy; no cats:
+    # the t=0/t=T-1 boundary term against h0 is a separate small bmm)
+    def dw_for(cols):
+        if reverse:
+            dp_main = dpre[:, :-1, :, cols]             # h_prev = h_all[t+1]
+            h_main = h_all[:, 1:]
+            dp_bound = dpre[:, -1, :, cols]             # h_prev = h0
+        else:
+            dp_main = dpre[:, 1:, :, cols]              # h_prev = h_all[t-1]
+            h_main = h_all[:, :-1]
+            dp_bound = dpre[:, 0, :, cols]
+        K = dp_main.shape[-1]
+        a = dp_main.reshape(B, (T - 1) * C, K).transpose(1, 2)
+        part = torch.bmm(a, h_main.reshape(B, (T - 1) * C, H))
+        ab = dp_bound.reshape(B, C, K).transpose(1, 2)
+        part = part + torch.bmm(ab, h0)
+        return unpi(part.sum(0, dtype=torch.float32))   # (K, H) natural rows
+
+    dw_rz = dw_for(slice(0, 2 * H))
+    dw_n = dw_for(slice(3 * H, 4 * H))
+    dw_hh = torch.cat([dw_rz, dw_n], dim=0)             # (3H, H) f32
+
+    # single-pass fused reductions (custom kernel): dxg, dgamma, dbeta4
+    # (dbeta4's 4th slice is sum of d_hh_n -> the n-part of db_hh)
+    dxg, dgamma, dbeta4 = ext.gru_bwd_reduce(dpre, gamma, x_gates)
+    s4 = dbeta4.sum(dim=0)                              # (4H,) f32, tiny
+    db_hh = torch.cat([s4[: 2 * H], s4[3 * H :]])
+    dbeta = dbeta4[:, : 3 * H]
+    return (
+        dxg,
+        dw_hh.to(w_hh.dtype),
+        db_hh,
+        dh0.to(h0.dtype),
+        dgamma.to(gamma.dtype),
+        dbeta.to(gamma.dtype),
+    )
+
+
+HEAD_FUSE_MAX_OUT = 32    # one K=32 MFMA covers the heads' output width
+
+
+class _FusedGRUHeads(torch.autograd.Function):
+    """GRU sequence + quantile-head projection as one autograd node, so the
+    backward never materializes the (B, T, C, H) head input gradient: the
+    kernel rebuilds grad_part @ w_head per step on the matrix unit."""
+
+    @staticmethod
+    def forward(ctx, x_gates, w_hh, b_hh, h0, gamma, beta, w_head, reverse):
+        ext = require_native("fused_gru_heads")
+        need_grad = any(ctx.needs_input_grad)
+        h_all, saves = ext.gru_seq_forward(
+            x_gates, w_hh, b_hh, h0, gamma, beta, bool(reverse), bool(need_grad)
         )
+        B, T, C, H = h_all.shape
+        # same GEMM as ops/linear_bigk.py's forward (3-D, leading-dim batch)
+        w = w_head.to(h_all.dtype)
+        part = torch.matmul(h_all.reshape(B, T * C, H), w.t())
+        ctx.save_for_backward(x_gates, w_hh, b_hh, h0, gamma, beta, h_all, saves, w)
+        ctx.reverse = bool(reverse)
+        ctx.w_head_dtype = w_head.dtype
+        return part.reshape(B, T, C, w.shape[0])
+
+    @staticmethod
+    def backward(ctx, grad_part):
+        ext = require_native("fused_gru_heads")
+        (x_gates, w_hh, b_hh, h0, gamma, beta, h_all, saves,
+         w) = ctx.saved_tensors
+        reverse = ctx.reverse
+        B, T, C, H = h_all.shape
+        O = w.shape[0]
+        g = grad_part.contiguous().to(h_all.dtype)
+        w_img, w_fwd = _bwd_weight_images(w_hh)
+        # (H, 32) bf16 B-operand image: w_head^T zero-padded along K
+        wh_img = torch.zeros(H, 32, device=w.device, dtype=torch.bfloat16)
+        wh_img[:, :O] = w.t()
+        dpre, dh0 = ext.gru_seq_backward_heads_kernel(
+            g, wh_img, w_img, w_fwd, x_gates, gamma, beta, b_hh, h0, h_all,
+            saves, reverse
+        )
+        # dW_head as in ops/linear_bigk.py: leading-dim-batched GEMMs, fp32 sum
+        dw_head = torch.bmm(g.reshape(B, T * C, O).transpose(1, 2),
+                            h_all.reshape(B, T * C, H)).sum(0, dtype=torch.float32)
+        return _bwd_reductions(ext, dpre, dh0, x_gates, w_hh, h0, gamma, h_all,
+                               reverse) + (dw_head.to(ctx.w_head_dtype), None)
 
 
 _WARNED_SHAPES = set()
@@ -246,3 +307,41 @@ def fused_gru_sequence(
         # autograd-tracked back to the fp32 master parameters
         return _FusedGRUSequence.apply(*args, reverse)
     return reference_gru_sequence(x_gates, w_hh, b_hh, h0, gamma, beta, reverse)
+
+
+def fused_gru_heads(
+    x_gates: torch.Tensor,       # (B, T, 3H)
+    w_hh: torch.Tensor,          # (3H, H)
+    b_hh: torch.Tensor,          # (3H,)
+    h0: torch.Tensor,            # (B, C, H)
+    gamma: torch.Tensor,         # (C, 3H)
+    beta: torch.Tensor,          # (C, 3H)
+    w_head: torch.Tensor,        # (O, H) head weights of this direction
+    reverse: bool = False,
+) -> torch.Tensor:
+    """``F.linear(fused_gru_sequence(...), w_head)`` -> (B, T, C, O), with the
+    head input gradient folded into the GRU backward kernel.
+
+    On the native kernel (GPU, H == 128, C >= 3) with ``O <= 32`` this is one
+    autograd node whose backward hands the O-wide ``grad_part`` straight to
+    the kernel.  Everywhere else (CPU, off-spec shapes, wider heads) it is
+    the differentiable composition of the two ops."""
+    O = w_head.shape[0]
+    native = (x_gates.is_cuda and gru_kernel_supports(h0.shape[2], h0.shape[1])
+              and O <= HEAD_FUSE_MAX_OUT)
+    if not native:
+        h_all = fused_gru_sequence(x_gates, w_hh, b_hh, h0, gamma, beta, reverse)
+        return torch.nn.functional.linear(h_all, w_head.to(h_all.dtype))
+    dt = x_gates.dtype
+    # dtype harmonization outside the Function (autograd-tracked casts);
+    # w_head keeps its dtype so its gradient leaves the fp32 sum unrounded
+    return _FusedGRUHeads.apply(
+        x_gates.contiguous(),
+        w_hh.to(dt).contiguous(),
+        b_hh.float().contiguous(),
+        h0.to(dt).contiguous(),
+        gamma.to(dt).contiguous(),
+        beta.to(dt).contiguous(),
+        w_head.contiguous(),
+        reverse,
+    )
