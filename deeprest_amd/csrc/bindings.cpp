@@ -47,6 +47,11 @@ void dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
                 const void* w_hh, const float* b_hh, const void* h0, void* h_all,
                 void* saves, int B, int TT, int C, int reverse, int save,
                 int fp8, int is_bf16, hipStream_t stream);
+int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
+                  const void* w_hh, const float* b_hh, const void* h0,
+                  const void* wh_fwd, void* out, void* h_last, int B, int TT,
+                  int C, int O, int reverse, int fp8, int is_bf16,
+                  hipStream_t stream);
 void dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
                 const void* w_fwd, const void* xg, const void* gamma,
                 const void* beta, const float* b_hh, const void* h0,
@@ -333,16 +338,13 @@ void fused_adam_capturable(at::Tensor meta_dev, int64_t nt, int64_t total,
 }
 
 // -------------------------------------------------------------------- gru
-std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
-                                        at::Tensor b_hh, at::Tensor h0,
-                                        at::Tensor gamma, at::Tensor beta,
-                                        bool reverse, bool save, bool fp8) {
-  TORCH_CHECK(!(fp8 && save), "fp8 GRU path is inference-only (no saves)");
-  const at::cuda::CUDAGuard guard(xg.device());
+// operand checks shared by the forward entries
+static void gru_forward_checks(const at::Tensor& xg, const at::Tensor& w_hh,
+                               const at::Tensor& b_hh, const at::Tensor& h0,
+                               const at::Tensor& gamma, const at::Tensor& beta) {
   check_dtype(xg, "x_gates");
   TORCH_CHECK(xg.dim() == 3, "x_gates must be (B, T, 3H)");
   TORCH_CHECK(h0.dim() == 3, "h0 must be (B, C, H)");
-  int B = (int)xg.size(0), TT = (int)xg.size(1);
   int C = (int)h0.size(1), H = (int)h0.size(2);
   TORCH_CHECK(H == 128, "fused GRU kernel requires hidden size 128, got ", H);
   TORCH_CHECK(C >= 3, "fused GRU kernel requires >= 3 components, got ", C);
@@ -358,6 +360,18 @@ std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
 
   TORCH_CHECK(xg.numel() < (1LL << 31),
               "x_gates too large for 32-bit staging offsets");
+}
+
+std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
+                                        at::Tensor b_hh, at::Tensor h0,
+                                        at::Tensor gamma, at::Tensor beta,
+                                        bool reverse, bool save, bool fp8) {
+  TORCH_CHECK(!(fp8 && save), "fp8 GRU path is inference-only (no saves)");
+  const at::cuda::CUDAGuard guard(xg.device());
+  gru_forward_checks(xg, w_hh, b_hh, h0, gamma, beta);
+  int B = (int)xg.size(0), TT = (int)xg.size(1);
+  int C = (int)h0.size(1), H = (int)h0.size(2);
+  auto dt = xg.scalar_type();
   auto h_all = at::empty({B, TT, C, H}, xg.options());
   auto saves = save ? at::empty({B, TT, C, 2 * H}, xg.options())
                     : at::empty({0}, xg.options());
@@ -370,6 +384,44 @@ std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
              save ? saves.data_ptr() : nullptr, B, TT, C, reverse ? 1 : 0,
              save ? 1 : 0, fp8 ? 1 : 0, dt == at::kBFloat16, cur_stream());
   return {h_all, saves};
+}
+
+// Inference decode: the GRU sequence with the quantile-head projection done
+// per step inside the kernel; h_all is never allocated.  wh_fwd: (32, H) bf16
+// with wh_fwd[o][k] = w_head[o][k] and zero rows for o >= O.  Returns
+// {out (B, T, C, O), h_last (B, C, H)}.  No host sync: graph-capturable.
+std::vector<at::Tensor> gru_seq_decode(at::Tensor xg, at::Tensor w_hh,
+                                       at::Tensor b_hh, at::Tensor h0,
+                                       at::Tensor gamma, at::Tensor beta,
+                                       at::Tensor wh_fwd, int64_t O, bool reverse,
+                                       bool fp8) {
+  const at::cuda::CUDAGuard guard(xg.device());
+  gru_forward_checks(xg, w_hh, b_hh, h0, gamma, beta);
+  int B = (int)xg.size(0), TT = (int)xg.size(1);
+  int C = (int)h0.size(1), H = (int)h0.size(2);
+  TORCH_CHECK(h0.size(0) == B && beta.sizes() == gamma.sizes() &&
+                  b_hh.numel() == 3 * H,
+              "gru decode: operand shapes do not match x_gates (B, T, 3H)");
+  TORCH_CHECK(O >= 1 && O <= 32, "fused head decode needs 1 <= O <= 32, got ", O);
+  TORCH_CHECK(wh_fwd.scalar_type() == at::kBFloat16 &&
+                  wh_fwd.sizes() == at::IntArrayRef({32, H}) &&
+                  wh_fwd.is_contiguous() && wh_fwd.is_cuda(),
+              "wh_fwd must be the (32, H) bf16 head weight image");
+  TORCH_CHECK((int64_t)B * TT * C * O < (1LL << 31),
+              "decode output too large for 32-bit store offsets");
+  auto dt = xg.scalar_type();
+  auto out = at::empty({B, TT, C, O}, xg.options());
+  auto h_last = at::empty({B, C, H}, xg.options());
+  auto w_gemm = w_hh.scalar_type() == at::kBFloat16
+                    ? w_hh
+                    : w_hh.to(at::kBFloat16);
+  int err = dr_gru_decode(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                          w_gemm.data_ptr(), b_hh.data_ptr<float>(),
+                          h0.data_ptr(), wh_fwd.data_ptr(), out.data_ptr(),
+                          h_last.data_ptr(), B, TT, C, (int)O, reverse ? 1 : 0,
+                          fp8 ? 1 : 0, dt == at::kBFloat16, cur_stream());
+  TORCH_CHECK(err == 0, "gru decode kernel launch failed (HIP error ", err, ")");
+  return {out, h_last};
 }
 
 // Sequential backward chain.  wh_img == nullptr: grad is grad_h (B, T, C, H).
@@ -534,6 +586,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gru_seq_forward", &gru_seq_forward, py::arg("xg"), py::arg("w_hh"),
         py::arg("b_hh"), py::arg("h0"), py::arg("gamma"), py::arg("beta"),
         py::arg("reverse"), py::arg("save"), py::arg("fp8") = false);
+  m.def("gru_seq_decode", &gru_seq_decode, py::arg("xg"), py::arg("w_hh"),
+        py::arg("b_hh"), py::arg("h0"), py::arg("gamma"), py::arg("beta"),
+        py::arg("wh_fwd"), py::arg("O"), py::arg("reverse"), py::arg("fp8") = false);
   m.def("gru_seq_backward_kernel", &gru_seq_backward_kernel);
   m.def("gru_seq_backward_heads_kernel", &gru_seq_backward_heads_kernel);
   m.def("gru_bwd_reduce", &gru_bwd_reduce);

@@ -169,7 +169,14 @@ __device__ __forceinline__ bf16x8 ld_frag<float>(const float* src) {
 // NSUB = 2: 8 waves / 128-row tile — 2 waves/SIMD (the kernel is
 // latency-stalled at 1 wave/SIMD); gamma/beta/b_hh then stream from L1/L2
 // instead of registers so each wave fits the 256-reg budget.
-template <typename T, bool SAVE, bool FP8 = false, int NSUB = 1>
+// HEADS = true (inference decode, SAVE = false): h_all is never written.
+// After each step's epilogue every wave multiplies its own 16 rows of the h
+// mirror by the quantile heads' weight image wh_fwd (32, H) bf16 —
+// wh_fwd[o][k] = w_head[o][k], exact zero rows for o >= O — on two more
+// 16-wide N-tiles and stores out (B, TT, C, O); the state after the last
+// processed step goes to h_last (B, C, H).  The image sits in LDS as 32 more
+// 256-byte rows behind the W image (8 KB, same swizzle, whatever FP8 is).
+template <typename T, bool SAVE, bool FP8 = false, int NSUB = 1, bool HEADS = false>
 __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     const T* __restrict__ xg,      // (B, TT, 3H)
     const T* __restrict__ gamma,   // (C, 3H)
@@ -179,13 +186,19 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     const T* __restrict__ h0,      // (B, C, H)
     T* __restrict__ h_all,         // (B, TT, C, H)
     T* __restrict__ saves,         // (B, TT, C, 4H) pi layout (SAVE only)
-    int B, int TT, int C, int reverse) {
+    int B, int TT, int C, int reverse,
+    const uint16_t* __restrict__ wh_fwd,  // HEADS: (32, H) bf16 head weight image
+    T* __restrict__ out,           // HEADS: (B, TT, C, O)
+    T* __restrict__ h_last,        // HEADS: (B, C, H)
+    int O) {
+  static_assert(!(HEADS && SAVE), "the head phase is inference-only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ELT = FP8 ? 1 : 2;             // GEMM-tile element bytes
   constexpr int BROWS = ROWS * NSUB;           // rows per block
   constexpr int BTHREADS = THREADS * NSUB;
   char* Wl = smem;
-  char* Hl = smem + G3H * H * ELT;
+  char* WHl = smem + G3H * H * ELT;            // (HEADS) 32 x 128 bf16 swizzled
+  char* Hl = WHl + (HEADS ? 32 * H * 2 : 0);
   char* XGl = Hl + BROWS * H * ELT;
 
   const int tid = threadIdx.x;
@@ -209,6 +222,14 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
           *reinterpret_cast<const uint64_t*>(q);
     } else {
       *reinterpret_cast<bf16x8*>(Wl + j * 256 + ((blk ^ (j & 15)) << 4)) = v;
+    }
+  }
+  if constexpr (HEADS) {
+    for (int id = tid; id < 32 * (H / 8); id += BTHREADS) {
+      int j = id / (H / 8);
+      int blk = id % (H / 8);
+      *reinterpret_cast<bf16x8*>(WHl + j * 256 + ((blk ^ (j & 15)) << 4)) =
+          *reinterpret_cast<const bf16x8*>(wh_fwd + j * H + blk * 8);
     }
   }
 
@@ -303,30 +324,39 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
       ++n_stage;
     }
   }
-  // h_all cooperative store chunks (4 per thread; row index fixed over t)
+  // h_all cooperative store chunks (4 per thread; row index fixed over t);
+  // HEADS has no h_all store, so nothing is filled in
   int64_t hout_bc[4];       // (b*TT + t_first)*C + c
   int hout_blk[4];
   int hout_lds[4];
   bool hout_live[4];
+  if constexpr (!HEADS) {
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    int id = tid + u * BTHREADS;            // BROWS*(H/8) = 4*BTHREADS
-    int row = id / (H / 8);
-    int blk = id % (H / 8);
-    int64_t r = r0 + row;
-    hout_live[u] = r < R;
-    int64_t rr = hout_live[u] ? r : (R - 1);
-    int b = (int)(rr / C), c = (int)(rr % C);
-    hout_bc[u] = ((int64_t)b * TT + t_first) * C + c;
-    hout_blk[u] = blk * 8;
-    hout_lds[u] = FP8 ? (row * 128 + ((blk ^ (row & 15)) << 3))
-                      : (row * 256 + ((blk ^ (row & 15)) << 4));
+    for (int u = 0; u < 4; ++u) {
+      int id = tid + u * BTHREADS;            // BROWS*(H/8) = 4*BTHREADS
+      int row = id / (H / 8);
+      int blk = id % (H / 8);
+      int64_t r = r0 + row;
+      hout_live[u] = r < R;
+      int64_t rr = hout_live[u] ? r : (R - 1);
+      int b = (int)(rr / C), c = (int)(rr % C);
+      hout_bc[u] = ((int64_t)b * TT + t_first) * C + c;
+      hout_blk[u] = blk * 8;
+      hout_lds[u] = FP8 ? (row * 128 + ((blk ^ (row & 15)) << 3))
+                        : (row * 256 + ((blk ^ (row & 15)) << 4));
+    }
   }
   // per-lane-row indices for the saves stores (pi layout)
   int64_t sv_bc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
     sv_bc[i] = ((int64_t)b_of[i] * TT + t_first) * C + comp_of[i];
+  // HEADS: the same row indices for the out stores, 32-bit (the binding
+  // checks out.numel() < 2^31)
+  int out_bc[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    out_bc[i] = (b_of[i] * TT + t_first) * C + comp_of[i];
   // per-wave A-fragment LDS offsets
   int afrag_off[KT];
   {
@@ -348,6 +378,7 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
   // ---- time loop ----
   int stage_toff = 0;                        // += dir*G3H per step (32-bit)
   int64_t bc_toff = 0;                       // += dirC per step (row-index units)
+  int out_toff = 0;                          // HEADS: the same, 32-bit
   const int stage_tstep = (reverse ? -1 : 1) * G3H;
   for (int step = 0; step < TT; ++step) {
     // A-fragments: this wave's 16 rows of the h tile, all 4 K-tiles
@@ -454,30 +485,91 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     }
     __syncthreads();
 
-    // ---- cooperative vectorized h_all store (reads the bf16 LDS tile) ----
+    if constexpr (HEADS) {
+      // ---- head phase: out[rows, t, :O] = h_t @ w_head^T ----
+      // A-fragments: this wave's own 16 rows of the just-written h mirror
+      // (the reads that open the next step).  FP8: the e4m3 mirror values
+      // are bf16-representable, so the conversion is exact and the heads see
+      // what the h_all store of the plain kernel would have written.
+      bf16x8 hfrag[KT];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (hout_live[u]) {
-        T* dst = h_all + (hout_bc[u] + bc_toff) * H + hout_blk[u];
+      for (int kt = 0; kt < KT; ++kt) {
         if constexpr (FP8) {
-          uint64_t raw = *reinterpret_cast<const uint64_t*>(Hl + hout_lds[u]);
+          uint64_t raw = *reinterpret_cast<const uint64_t*>(Hl + afrag_off[kt]);
           const uint8_t* q = reinterpret_cast<const uint8_t*>(&raw);
+          uint16_t p[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             __hip_fp8_e4m3 x;
             x.__x = q[e];
-            stf(dst + e, float(x));
+            p[e] = f2bf(float(x));
           }
+          hfrag[kt] = *reinterpret_cast<const bf16x8*>(p);
         } else {
-          st_frag(dst, lds_read8(Hl, hout_lds[u]));
+          hfrag[kt] = lds_read8(Hl, afrag_off[kt]);
         }
       }
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        if (nt * 16 < O) {                     // wave-uniform
+          f32x4 a = {0.f, 0.f, 0.f, 0.f};
+          const int j = nt * 16 + c_col;       // head output column
+#pragma unroll
+          for (int kt = 0; kt < KT; ++kt) {
+            const int k0 = kt * 32 + (lane >> 4) * 8;
+            bf16x8 bfrag = lds_read8(WHl, swz(j, k0));
+            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hfrag[kt], bfrag, a, 0, 0, 0);
+          }
+          if (j < O) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (live[i]) stf(out + (out_bc[i] + out_toff) * O + j, a[i]);
+          }
+        }
+      }
+      stage_toff += stage_tstep;
+      out_toff += dirC;
+      // no end-of-step barrier: a wave's h-mirror rows are written and read
+      // by that wave alone once the cooperative h_all store is gone, and the
+      // next xg staging is ordered behind every wave's epilogue reads by the
+      // barrier above.
+    } else {
+      // ---- cooperative vectorized h_all store (reads the bf16 LDS tile) ----
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (hout_live[u]) {
+          T* dst = h_all + (hout_bc[u] + bc_toff) * H + hout_blk[u];
+          if constexpr (FP8) {
+            uint64_t raw = *reinterpret_cast<const uint64_t*>(Hl + hout_lds[u]);
+            const uint8_t* q = reinterpret_cast<const uint8_t*>(&raw);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              __hip_fp8_e4m3 x;
+              x.__x = q[e];
+              stf(dst + e, float(x));
+            }
+          } else {
+            st_frag(dst, lds_read8(Hl, hout_lds[u]));
+          }
+        }
+      }
+      stage_toff += stage_tstep;
+      bc_toff += dirC;
+      // barrier covers both: h-store reads done AND next step's a-frag reads
+      // see the same consistent tile until the next epilogue writes it.
+      __syncthreads();
     }
-    stage_toff += stage_tstep;
-    bc_toff += dirC;
-    // barrier covers both: h-store reads done AND next step's a-frag reads
-    // see the same consistent tile until the next epilogue writes it.
-    __syncthreads();
+  }
+
+  if constexpr (HEADS) {
+    // ---- h_last: the fp32 register state, rounded once to the IO dtype ----
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (!live[i]) continue;
+      T* dst = h_last + r_abs[i] * H + c_col;   // row b*C + c is r_abs itself
+#pragma unroll
+      for (int nt = 0; nt < 8; ++nt) stf(dst + nt * 16, h[i][nt]);
+    }
   }
 }
 
@@ -968,30 +1060,87 @@ static void gru_fwd_launch_t(const void* xg, const void* gamma, const void* beta
                          dim3(2 * THREADS), LDS_FWD_8W, stream, (const T*)xg,
                          (const T*)gamma, (const T*)beta, (const uint16_t*)w_gemm,
                          b_hh, (const T*)h0, (T*)h_all, (T*)saves, B, TT, C,
-                         reverse);
+                         reverse, nullptr, nullptr, nullptr, 0);
     else
       hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 2>), dim3(tiles128),
                          dim3(2 * THREADS), LDS_FWD_8W, stream, (const T*)xg,
                          (const T*)gamma, (const T*)beta, (const uint16_t*)w_gemm,
                          b_hh, (const T*)h0, (T*)h_all, (T*)saves, B, TT, C,
-                         reverse);
+                         reverse, nullptr, nullptr, nullptr, 0);
     return;
   }
   if (fp8)
     hipLaunchKernelGGL((gru_fwd_kernel<T, false, true>), dim3(grid), dim3(THREADS),
                        LDS_FWD_FP8, stream, (const T*)xg, (const T*)gamma,
                        (const T*)beta, (const uint16_t*)w_gemm, b_hh, (const T*)h0,
-                       (T*)h_all, (T*)saves, B, TT, C, reverse);
+                       (T*)h_all, (T*)saves, B, TT, C, reverse, nullptr, nullptr,
+                       nullptr, 0);
   else if (save)
     hipLaunchKernelGGL((gru_fwd_kernel<T, true>), dim3(grid), dim3(THREADS),
                        LDS_FWD_TOTAL, stream, (const T*)xg, (const T*)gamma,
                        (const T*)beta, (const uint16_t*)w_gemm, b_hh, (const T*)h0,
-                       (T*)h_all, (T*)saves, B, TT, C, reverse);
+                       (T*)h_all, (T*)saves, B, TT, C, reverse, nullptr, nullptr,
+                       nullptr, 0);
   else
     hipLaunchKernelGGL((gru_fwd_kernel<T, false>), dim3(grid), dim3(THREADS),
                        LDS_FWD_TOTAL, stream, (const T*)xg, (const T*)gamma,
                        (const T*)beta, (const uint16_t*)w_gemm, b_hh, (const T*)h0,
-                       (T*)h_all, (T*)saves, B, TT, C, reverse);
+                       (T*)h_all, (T*)saves, B, TT, C, reverse, nullptr, nullptr,
+                       nullptr, 0);
+}
+
+// HEADS decode: same three variants behind the same dispatch conditions as
+// gru_fwd_launch_t.  The 8 KB head weight image joins every variant's LDS:
+// 147,456 B (4-wave), 90,112 B (FP8), 163,840 B (8-wave: all a workgroup may
+// declare).
+constexpr int LDS_WH = 32 * H * 2;  // 8192 B
+
+template <typename T>
+static int gru_decode_launch_t(const void* xg, const void* gamma, const void* beta,
+                               const void* w_gemm, const float* b_hh,
+                               const void* h0, const void* wh_fwd, void* out,
+                               void* h_last, int B, int TT, int C, int O,
+                               int reverse, int fp8, hipStream_t stream) {
+  int64_t R = (int64_t)B * C;
+  int grid = (int)((R + ROWS - 1) / ROWS);
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&gru_fwd_kernel<T, false, false, 1, true>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_TOTAL + LDS_WH);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(
+          reinterpret_cast<const void*>(&gru_fwd_kernel<T, false, true, 1, true>),
+          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_FP8 + LDS_WH);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(
+          reinterpret_cast<const void*>(&gru_fwd_kernel<T, false, false, 2, true>),
+          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_8W + LDS_WH);
+    if (e != hipSuccess) return (int)e;
+    attr_set = true;
+  }
+  int tiles128 = (int)((R + 2 * ROWS - 1) / (2 * ROWS));
+  if (!fp8 && tiles128 >= 192 && C >= 5)
+    hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 2, true>), dim3(tiles128),
+                       dim3(2 * THREADS), LDS_FWD_8W + LDS_WH, stream,
+                       (const T*)xg, (const T*)gamma, (const T*)beta,
+                       (const uint16_t*)w_gemm, b_hh, (const T*)h0, nullptr,
+                       nullptr, B, TT, C, reverse, (const uint16_t*)wh_fwd,
+                       (T*)out, (T*)h_last, O);
+  else if (fp8)
+    hipLaunchKernelGGL((gru_fwd_kernel<T, false, true, 1, true>), dim3(grid),
+                       dim3(THREADS), LDS_FWD_FP8 + LDS_WH, stream, (const T*)xg,
+                       (const T*)gamma, (const T*)beta, (const uint16_t*)w_gemm,
+                       b_hh, (const T*)h0, nullptr, nullptr, B, TT, C, reverse,
+                       (const uint16_t*)wh_fwd, (T*)out, (T*)h_last, O);
+  else
+    hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 1, true>), dim3(grid),
+                       dim3(THREADS), LDS_FWD_TOTAL + LDS_WH, stream,
+                       (const T*)xg, (const T*)gamma, (const T*)beta,
+                       (const uint16_t*)w_gemm, b_hh, (const T*)h0, nullptr,
+                       nullptr, B, TT, C, reverse, (const uint16_t*)wh_fwd,
+                       (T*)out, (T*)h_last, O);
+  return (int)hipGetLastError();   // a rejected launch is the caller's error
 }
 
 template <typename T, bool FUSED>
@@ -1080,6 +1229,23 @@ void dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
   else
     dr::gru_fwd_launch_t<float>(xg, gamma, beta, w_hh, b_hh, h0, h_all, saves,
                                 B, TT, C, reverse, save, fp8, stream);
+}
+
+// Inference decode: GRU sequence + head projection, no h_all.  wh_fwd is the
+// (32, H) bf16 head weight image, rows >= O exact zero.  Returns the HIP
+// error of the attribute setup or the launch (0 = success).
+int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
+                  const void* w_hh, const float* b_hh, const void* h0,
+                  const void* wh_fwd, void* out, void* h_last, int B, int TT,
+                  int C, int O, int reverse, int fp8, int is_bf16,
+                  hipStream_t stream) {
+  if (is_bf16)
+    return dr::gru_decode_launch_t<uint16_t>(xg, gamma, beta, w_hh, b_hh, h0,
+                                             wh_fwd, out, h_last, B, TT, C, O,
+                                             reverse, fp8, stream);
+  return dr::gru_decode_launch_t<float>(xg, gamma, beta, w_hh, b_hh, h0, wh_fwd,
+                                        out, h_last, B, TT, C, O, reverse, fp8,
+                                        stream);
 }
 
 // wh_img == nullptr: grad is grad_h (B, TT, C, H), the unfused path.

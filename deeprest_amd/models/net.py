@@ -35,8 +35,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..data.featurize import FeaturizedData
-from ..ops import (dropout_add, dropout_add_layer_norm, fused_gru_heads,
-                   fused_gru_sequence, layer_norm, mha_forward, pinball_loss)
+from ..ops import (dropout_add, dropout_add_layer_norm, fused_gru_decode,
+                   fused_gru_heads, fused_gru_sequence, layer_norm, mha_forward,
+                   pinball_loss)
 from ..ops.gru import HEAD_FUSE_MAX_OUT, gru_kernel_supports
 from ..ops.linear_bigk import bigk_linear
 
@@ -154,6 +155,13 @@ class DeepRestNetConfig:
                                           # native GRU kernel runs and head
                                           # dropout is inactive; same
                                           # parameters and state_dict keys
+    fused_head_decode: bool = False       # inference (eval, no grad, GPU):
+                                          # decoder + quantile heads as one
+                                          # kernel per direction that never
+                                          # writes the (B,T,C,H) hidden
+                                          # sequence; forward_long then keeps
+                                          # only head-wide outputs per chunk;
+                                          # same parameters and state_dict keys
 
     def to_dict(self) -> dict:
         return {
@@ -165,6 +173,7 @@ class DeepRestNetConfig:
             "fp8_inference": self.fp8_inference, "linear_bias": self.linear_bias,
             "fused_residual_norm": self.fused_residual_norm,
             "fused_head_grad": self.fused_head_grad,
+            "fused_head_decode": self.fused_head_decode,
         }
 
 
@@ -337,6 +346,24 @@ class _GRUDecoderBank(nn.Module):
             out = part if out is None else out + part
         return out
 
+    def decode_heads(self, enc: torch.Tensor, comp: torch.Tensor,
+                     w_heads: Sequence[torch.Tensor], fp8: bool = False,
+                     d: int = 0):
+        """Inference decode of direction ``d`` (ops.fused_gru_decode):
+        returns ``(part (B, T, C, O), h_last (B, C, H))`` with ``part`` that
+        direction's head output; the hidden sequence is never materialized."""
+        B = enc.shape[0]
+        C = comp.shape[0]
+        sfx = "_r" if d else ""
+        xg = getattr(self, "x_proj" + sfx)(enc)                # (B, T, 3H)
+        gamma = getattr(self, "cond_gamma" + sfx)(comp)        # (C, 3H)
+        beta = getattr(self, "cond_beta" + sfx)(comp)
+        h0 = torch.tanh(getattr(self, "h0_proj" + sfx)(comp))
+        h0 = h0.unsqueeze(0).expand(B, C, self.hidden).contiguous()
+        return fused_gru_decode(xg, getattr(self, "w_hh" + sfx),
+                                getattr(self, "b_hh" + sfx), h0, gamma, beta,
+                                w_heads[d], reverse=bool(d), fp8=fp8)
+
 
 # -------------------------------------------------------------------- model
 class DeepRestNet(nn.Module):
@@ -408,6 +435,13 @@ class DeepRestNet(nn.Module):
         comp = self.graph()                                   # (C, comp_dim)
         fp8 = (self.cfg.fp8_inference and not self.training
                and traffic.is_cuda and not torch.is_grad_enabled())
+        if self._use_head_decode(x, comp):
+            w_dirs = self._head_weights_per_dir()
+            out = None
+            for d in range(len(w_dirs)):
+                part, _ = self.decoder.decode_heads(x, comp, w_dirs, fp8, d)
+                out = part if out is None else out + part
+            return self._finish_heads(out)
         if self._use_fused_heads(x, comp, fp8):
             H = self.cfg.hidden
             w_all = self._head_weights()
@@ -430,6 +464,24 @@ class DeepRestNet(nn.Module):
         if self.training and self.dropout.p > 0:
             return False
         return len(self.heads) * len(self.cfg.quantiles) <= HEAD_FUSE_MAX_OUT
+
+    def _use_head_decode(self, enc: torch.Tensor, comp: torch.Tensor) -> bool:
+        """cfg.fused_head_decode applies to inference only — eval mode, grad
+        disabled, GPU input — when the decoder runs the native GRU kernel and
+        all heads together fit its two 16-wide output tiles."""
+        if not self.cfg.fused_head_decode or self.training:
+            return False
+        if torch.is_grad_enabled() or not enc.is_cuda:
+            return False
+        if not gru_kernel_supports(self.cfg.hidden, comp.shape[0]):
+            return False
+        return len(self.heads) * len(self.cfg.quantiles) <= HEAD_FUSE_MAX_OUT
+
+    def _head_weights_per_dir(self) -> List[torch.Tensor]:
+        H = self.cfg.hidden
+        w_all = self._head_weights()
+        dirs = 2 if self.cfg.bidirectional else 1
+        return [w_all[:, d * H : (d + 1) * H].contiguous() for d in range(dirs)]
 
     def _encode_fused(self, x: torch.Tensor) -> torch.Tensor:
         """Encoder stack with cfg.fused_residual_norm: carries the residual
@@ -488,6 +540,11 @@ class DeepRestNet(nn.Module):
         bidirectional, a reverse sweep right->left — so recurrence is exact
         over the whole horizon while peak memory is O(chunk).
 
+        Without cfg.fused_head_decode every chunk's (B, Tc, C, H) hidden
+        sequence is kept per direction until the heads run at the end; with
+        it (GPU, eval mode) each chunk keeps only its (B, Tc, C, R*Q) head
+        output and the carried state.
+
         traffic: (B, T_total, P) -> (B, T_total, M, Q)
         """
         B, T_total, P = traffic.shape
@@ -514,6 +571,10 @@ class DeepRestNet(nn.Module):
         # fp8 MFMA decode (BASELINE config 5) applies to the long-horizon
         # path exactly as to forward()
         fp8 = bool(cfg.fp8_inference and traffic.is_cuda)
+        # head decode inside the GRU kernel: per chunk only the head-wide
+        # part and the carried state survive
+        use_dec = self._use_head_decode(traffic, comp)
+        w_dirs = self._head_weights_per_dir() if use_dec else None
 
         # forward sweep
         h_f = torch.tanh(dec.h0_proj(comp)).unsqueeze(0).expand(B, C, H).contiguous().to(dt)
@@ -525,6 +586,12 @@ class DeepRestNet(nn.Module):
             enc = encode(traffic[:, s:e])
             enc_cache.append(enc)
             xg = dec.x_proj(enc)
+            if use_dec:
+                part, h_f = fused_gru_decode(xg, dec.w_hh, dec.b_hh, h_f, gamma,
+                                             beta, w_dirs[0], reverse=False,
+                                             fp8=fp8)
+                fwd_outs.append(part)
+                continue
             out = fused_gru_sequence(xg, dec.w_hh, dec.b_hh, h_f, gamma, beta,
                                      reverse=False, fp8=fp8)
             h_f = out[:, -1].contiguous()
@@ -537,6 +604,12 @@ class DeepRestNet(nn.Module):
             rev_outs = [None] * len(chunks)
             for ci in range(len(chunks) - 1, -1, -1):
                 xg_r = dec.x_proj_r(enc_cache[ci])
+                if use_dec:
+                    part, h_r = fused_gru_decode(xg_r, dec.w_hh_r, dec.b_hh_r,
+                                                 h_r, gamma_r, beta_r, w_dirs[1],
+                                                 reverse=True, fp8=fp8)
+                    rev_outs[ci] = part
+                    continue
                 out_r = fused_gru_sequence(xg_r, dec.w_hh_r, dec.b_hh_r, h_r,
                                            gamma_r, beta_r, reverse=True,
                                            fp8=fp8)
@@ -546,6 +619,10 @@ class DeepRestNet(nn.Module):
         else:
             h_chunks = [(f,) for f in fwd_outs]
 
+        if use_dec:
+            preds = [self._finish_heads(sum(parts[1:], parts[0]))
+                     for parts in h_chunks]
+            return torch.cat(preds, dim=1)
         preds = [self._apply_heads(h_dirs) for h_dirs in h_chunks]
         return torch.cat(preds, dim=1)
 

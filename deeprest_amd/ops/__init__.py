@@ -13,7 +13,8 @@ can never masquerade as kernel coverage.
 """
 
 from .native import native_available, require_native, load_native
-from .gru import fused_gru_heads, fused_gru_sequence, reference_gru_sequence
+from .gru import (fused_gru_decode, fused_gru_heads, fused_gru_sequence,
+                  reference_gru_sequence)
 from .layernorm import layer_norm, reference_layer_norm
 from .residual_norm import (dropout_add, dropout_add_layer_norm, philox_keep_mask,
                             reference_dropout_add_layer_norm)
@@ -27,6 +28,7 @@ __all__ = [
     "load_native",
     "fused_gru_sequence",
     "fused_gru_heads",
+    "fused_gru_decode",
     "reference_gru_sequence",
     "layer_norm",
     "reference_layer_norm",

@@ -345,3 +345,55 @@ def fused_gru_heads(
         w_head.contiguous(),
         reverse,
     )
+
+
+def fused_gru_decode(
+    x_gates: torch.Tensor,       # (B, T, 3H)
+    w_hh: torch.Tensor,          # (3H, H)
+    b_hh: torch.Tensor,          # (3H,)
+    h0: torch.Tensor,            # (B, C, H)
+    gamma: torch.Tensor,         # (C, 3H)
+    beta: torch.Tensor,          # (C, 3H)
+    w_head: torch.Tensor,        # (O, H) head weights of this direction
+    reverse: bool = False,
+    fp8: bool = False,
+):
+    """Inference decode: ``(F.linear(h_all, w_head), h_all[:, last])`` with
+    ``h_all = fused_gru_sequence(...)`` -> ``out (B, T, C, O)`` and ``h_last
+    (B, C, H)``, the state after the last processed step (t = T-1 forward,
+    t = 0 reverse) for carrying across chunks.
+
+    On the native kernel (GPU, H == 128, C >= 3) with ``O <= 32`` the head
+    projection runs per step inside the GRU kernel and ``h_all`` is never
+    materialized.  Everywhere else (CPU, off-spec shapes, wider heads) it is
+    the composition of the two ops.  Not differentiable: raises when grad
+    mode is on and an input requires grad."""
+    if torch.is_grad_enabled() and any(
+        t.requires_grad
+        for t in (x_gates, w_hh, b_hh, h0, gamma, beta, w_head)
+    ):
+        raise RuntimeError("fused_gru_decode is inference-only (no autograd)")
+    O = w_head.shape[0]
+    native = (x_gates.is_cuda and gru_kernel_supports(h0.shape[2], h0.shape[1])
+              and O <= HEAD_FUSE_MAX_OUT)
+    if not native:
+        h_all = fused_gru_sequence(x_gates, w_hh, b_hh, h0, gamma, beta,
+                                   reverse, fp8=fp8)
+        out = torch.nn.functional.linear(h_all, w_head.to(h_all.dtype))
+        return out, h_all[:, 0 if reverse else -1]
+    ext = require_native("fused_gru_decode")
+    dt = x_gates.dtype
+    # (32, H) bf16 B-operand image: w_head zero-padded along the output axis
+    wh_fwd = torch.zeros(32, w_head.shape[1], device=x_gates.device,
+                         dtype=torch.bfloat16)
+    wh_fwd[:O] = w_head
+    out, h_last = ext.gru_seq_decode(
+        x_gates.contiguous(),
+        w_hh.to(dt).contiguous(),
+        b_hh.float().contiguous(),
+        h0.to(dt).contiguous(),
+        gamma.to(dt).contiguous(),
+        beta.to(dt).contiguous(),
+        wh_fwd, O, bool(reverse), bool(fp8),
+    )
+    return out, h_last
