@@ -26,14 +26,21 @@ constexpr int K_STRIDE = DMAX * 2 + 16;      // K tile: [key][d]
 constexpr int V_STRIDE = KT_KEYS * 2 + 16;   // V^T tile: [d][key]
 constexpr int P_STRIDE = KT_KEYS * 2 + 16;   // P tile:  [qrow][key]
 
-template <typename T>
+// VARLEN = true (inference only): sample b = bh / n_heads is valid at
+// t < L = clamp(kv_len[b], 1, T_len).  Keys >= L are absent (never staged,
+// never scored), query tiles at or past L store zeros and leave before the
+// first barrier, rows >= L of a partly valid tile store zeros.  Strides keep
+// using T_len.
+template <typename T, bool VARLEN = false>
 __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
     const T* __restrict__ q,   // (BH, T, D)
     const T* __restrict__ k,
     const T* __restrict__ v,
     T* __restrict__ o,         // (BH, T, D)
     float* __restrict__ lse,   // (BH, T)
-    int T_len, int D, float scale) {
+    int T_len, int D, float scale,
+    const int* __restrict__ kv_len,  // VARLEN: (B,) int32
+    int n_heads) {
   __shared__ __attribute__((aligned(16))) char k_lds[KT_KEYS * K_STRIDE];
   __shared__ __attribute__((aligned(16))) char vt_lds[DMAX * V_STRIDE];
   __shared__ __attribute__((aligned(16))) char p_lds[QT * P_STRIDE];
@@ -51,7 +58,27 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
   const int c_col = lane & 15;
   const int rgrp = lane >> 4;
 
-  // ---- Q fragments: this wave's 16 rows, zero-padded past D and T ----
+  // valid length of this block's sample: T_len itself without VARLEN
+  int L = T_len;
+  if constexpr (VARLEN) {
+    L = std::min(std::max(kv_len[blockIdx.y / n_heads], 1), T_len);
+    if (q0 >= L) {                       // block-uniform: a fully padded tile
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        int row = q0 + wv * 16 + rgrp * 4 + i;
+        if (row >= T_len) continue;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+          int d = nt * 16 + c_col;
+          if (d < D) stf(o + (bh * T_len + row) * D + d, 0.f);
+        }
+        if (c_col == 0) lse[bh * T_len + row] = 0.f;
+      }
+      return;
+    }
+  }
+
+  // ---- Q fragments: this wave's 16 rows, zero-padded past D and L ----
   const int n_kt_qk = (D + 31) / 32;  // K-tiles in QK^T (K dim = D)
   bf16x8 qfrag[2];
   {
@@ -62,7 +89,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         int d = kt * 32 + rgrp * 8 + j;
-        float val = (qrow < T_len && d < D) ? ldf(qb + (int64_t)qrow * D + d) : 0.f;
+        float val = (qrow < L && d < D) ? ldf(qb + (int64_t)qrow * D + d) : 0.f;
         tmp[j] = f2bf(val);
       }
       qfrag[kt] = *reinterpret_cast<bf16x8*>(tmp);
@@ -82,7 +109,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
 #pragma unroll
     for (int e = 0; e < 4; ++e) o_acc[nt][e] = 0.f;
 
-  const int n_key_tiles = (T_len + KT_KEYS - 1) / KT_KEYS;
+  const int n_key_tiles = (L + KT_KEYS - 1) / KT_KEYS;
   for (int ktile = 0; ktile < n_key_tiles; ++ktile) {
     const int key0 = ktile * KT_KEYS;
 
@@ -96,7 +123,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         int d = blk * 8 + e;
-        dst[e] = f2bf((krow < T_len && d < D) ? ldf(kb + (int64_t)krow * D + d) : 0.f);
+        dst[e] = f2bf((krow < L && d < D) ? ldf(kb + (int64_t)krow * D + d) : 0.f);
       }
     }
     for (int id = tid; id < DMAX * KT_KEYS / 8; id += A_THREADS) {
@@ -106,7 +133,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         int key = key0 + kb8 * 8 + e;
-        dst[e] = f2bf((key < T_len && d < D) ? ldf(vb + (int64_t)key * D + d) : 0.f);
+        dst[e] = f2bf((key < L && d < D) ? ldf(vb + (int64_t)key * D + d) : 0.f);
       }
     }
     __syncthreads();
@@ -139,7 +166,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
       int key = key0 + nt * 16 + c_col;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float s = (key < T_len) ? s_acc[nt][i] * scale : -1e30f;
+        float s = (key < L) ? s_acc[nt][i] * scale : -1e30f;
         p[nt][i] = s;
         pmax[i] = fmaxf(pmax[i], s);
       }
@@ -198,15 +225,19 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
     int row = q0 + wv * 16 + rgrp * 4 + i;
     if (row >= T_len) continue;
     float inv_l = (l_run[i] > 0.f) ? 1.f / l_run[i] : 0.f;
+    // VARLEN: rows >= L of a partly valid tile store exact zeros (a select:
+    // whatever the padded q row produced never reaches memory)
+    const bool pad = VARLEN && row >= L;
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {  // compile-time index (rule 20)
       if (nt >= n_d_tiles) continue;
       int d = nt * 16 + c_col;
       if (d < D)
-        stf(o + (bh * T_len + row) * D + d, o_acc[nt][i] * inv_l);
+        stf(o + (bh * T_len + row) * D + d, pad ? 0.f : o_acc[nt][i] * inv_l);
     }
     if (c_col == 0)
-      lse[bh * T_len + row] = m_run[i] + __logf(fmaxf(l_run[i], 1e-30f));
+      lse[bh * T_len + row] =
+          pad ? 0.f : m_run[i] + __logf(fmaxf(l_run[i], 1e-30f));
   }
 }
 
@@ -491,11 +522,16 @@ __global__ __launch_bounds__(A_THREADS) void mha_bwd_kernel(
 template <typename T>
 static void mha_fwd_launch_t(const void* q, const void* k, const void* v, void* o,
                              float* lse, int64_t BH, int T_len, int D, float scale,
-                             hipStream_t stream) {
+                             const int* kv_len, int n_heads, hipStream_t stream) {
   dim3 grid((T_len + QT - 1) / QT, (unsigned)BH);
-  hipLaunchKernelGGL((mha_fwd_kernel<T>), grid, dim3(A_THREADS), 0, stream,
-                     (const T*)q, (const T*)k, (const T*)v, (T*)o, lse, T_len, D,
-                     scale);
+  if (kv_len != nullptr)
+    hipLaunchKernelGGL((mha_fwd_kernel<T, true>), grid, dim3(A_THREADS), 0,
+                       stream, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse,
+                       T_len, D, scale, kv_len, n_heads);
+  else
+    hipLaunchKernelGGL((mha_fwd_kernel<T, false>), grid, dim3(A_THREADS), 0,
+                       stream, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse,
+                       T_len, D, scale, nullptr, n_heads);
 }
 
 template <typename T>
@@ -525,13 +561,17 @@ void dr_mha_bwd(const void* q, const void* k, const void* v, const void* o,
                                 D, scale, stream);
 }
 
+// kv_len == nullptr: every sample is T_len long (the training kernel).
+// Otherwise (B,) int32 per-sample lengths on the device, BH = B * n_heads.
 void dr_mha_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                 int64_t BH, int T_len, int D, float scale, int is_bf16,
-                hipStream_t stream) {
+                const int* kv_len, int n_heads, hipStream_t stream) {
   if (is_bf16)
-    dr::mha_fwd_launch_t<uint16_t>(q, k, v, o, lse, BH, T_len, D, scale, stream);
+    dr::mha_fwd_launch_t<uint16_t>(q, k, v, o, lse, BH, T_len, D, scale, kv_len,
+                                   n_heads, stream);
   else
-    dr::mha_fwd_launch_t<float>(q, k, v, o, lse, BH, T_len, D, scale, stream);
+    dr::mha_fwd_launch_t<float>(q, k, v, o, lse, BH, T_len, D, scale, kv_len,
+                                n_heads, stream);
 }
 
 }  // extern "C"

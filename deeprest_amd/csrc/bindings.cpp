@@ -51,7 +51,7 @@ int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
                   const void* w_hh, const float* b_hh, const void* h0,
                   const void* wh_fwd, void* out, void* h_last, int B, int TT,
                   int C, int O, int reverse, int fp8, int is_bf16,
-                  hipStream_t stream);
+                  const int* lens, hipStream_t stream);
 void dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
                 const void* w_fwd, const void* xg, const void* gamma,
                 const void* beta, const float* b_hh, const void* h0,
@@ -64,7 +64,7 @@ void dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
                        hipStream_t stream);
 void dr_mha_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                 int64_t BH, int T_len, int D, float scale, int is_bf16,
-                hipStream_t stream);
+                const int* kv_len, int n_heads, hipStream_t stream);
 void dr_mha_bwd(const void* q, const void* k, const void* v, const void* o,
                 const void* dout, const float* lse, float* dq, void* dk, void* dv,
                 int64_t BH, int T_len, int D, float scale, int is_bf16,
@@ -82,6 +82,23 @@ void check_dtype(const at::Tensor& t, const char* name) {
 
 hipStream_t cur_stream() {
   return at::cuda::getCurrentCUDAStream().stream();
+}
+
+// optional per-sample lengths of the inference kernels: (B,) int32 on the
+// input's device.  The VALUES are not checked (no host sync): the kernels
+// clamp each one to [1, T] themselves.
+const int* lengths_ptr(const c10::optional<at::Tensor>& lengths,
+                       const at::Tensor& like, int64_t B, const char* name) {
+  if (!lengths.has_value()) return nullptr;
+  const at::Tensor& l = *lengths;
+  TORCH_CHECK(l.scalar_type() == at::kInt, name, " must be int32, got ",
+              l.scalar_type());
+  TORCH_CHECK(l.is_cuda() && l.device() == like.device(), name,
+              " must be on the input's device");
+  TORCH_CHECK(l.is_contiguous() && l.numel() == B, name,
+              " must be contiguous with one entry per batch sample (", B,
+              "), got ", l.numel());
+  return l.data_ptr<int>();
 }
 
 // ------------------------------------------------------------- layer norm
@@ -390,11 +407,15 @@ std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
 // per step inside the kernel; h_all is never allocated.  wh_fwd: (32, H) bf16
 // with wh_fwd[o][k] = w_head[o][k] and zero rows for o >= O.  Returns
 // {out (B, T, C, O), h_last (B, C, H)}.  No host sync: graph-capturable.
+// lengths (optional, (B,) int32): sample b runs its own steps t < lengths[b]
+// only — out is zero at the padded positions and h_last is each row's state
+// after its own last valid step.
 std::vector<at::Tensor> gru_seq_decode(at::Tensor xg, at::Tensor w_hh,
                                        at::Tensor b_hh, at::Tensor h0,
                                        at::Tensor gamma, at::Tensor beta,
                                        at::Tensor wh_fwd, int64_t O, bool reverse,
-                                       bool fp8) {
+                                       bool fp8,
+                                       c10::optional<at::Tensor> lengths) {
   const at::cuda::CUDAGuard guard(xg.device());
   gru_forward_checks(xg, w_hh, b_hh, h0, gamma, beta);
   int B = (int)xg.size(0), TT = (int)xg.size(1);
@@ -409,8 +430,11 @@ std::vector<at::Tensor> gru_seq_decode(at::Tensor xg, at::Tensor w_hh,
               "wh_fwd must be the (32, H) bf16 head weight image");
   TORCH_CHECK((int64_t)B * TT * C * O < (1LL << 31),
               "decode output too large for 32-bit store offsets");
+  const int* lens = lengths_ptr(lengths, xg, B, "gru decode lengths");
   auto dt = xg.scalar_type();
-  auto out = at::empty({B, TT, C, O}, xg.options());
+  // with lengths the kernel stores valid positions only: padding stays zero
+  auto out = lens ? at::zeros({B, TT, C, O}, xg.options())
+                  : at::empty({B, TT, C, O}, xg.options());
   auto h_last = at::empty({B, C, H}, xg.options());
   auto w_gemm = w_hh.scalar_type() == at::kBFloat16
                     ? w_hh
@@ -419,7 +443,7 @@ std::vector<at::Tensor> gru_seq_decode(at::Tensor xg, at::Tensor w_hh,
                           w_gemm.data_ptr(), b_hh.data_ptr<float>(),
                           h0.data_ptr(), wh_fwd.data_ptr(), out.data_ptr(),
                           h_last.data_ptr(), B, TT, C, (int)O, reverse ? 1 : 0,
-                          fp8 ? 1 : 0, dt == at::kBFloat16, cur_stream());
+                          fp8 ? 1 : 0, dt == at::kBFloat16, lens, cur_stream());
   TORCH_CHECK(err == 0, "gru decode kernel launch failed (HIP error ", err, ")");
   return {out, h_last};
 }
@@ -531,8 +555,12 @@ std::vector<at::Tensor> gru_bwd_reduce(at::Tensor dpre, at::Tensor gamma,
 }
 
 // -------------------------------------------------------------------- mha
+// kv_lengths (optional, (B,) int32): keys >= kv_lengths[b] are absent and
+// rows of o / lse at or past it are zero (inference only; mha_backward does
+// not know about lengths).
 std::vector<at::Tensor> mha_forward(at::Tensor q, at::Tensor k, at::Tensor v,
-                                    double scale) {
+                                    double scale,
+                                    c10::optional<at::Tensor> kv_lengths) {
   const at::cuda::CUDAGuard guard(q.device());
   check_dtype(q, "q");
   TORCH_CHECK(q.dim() == 4, "q must be (B, H, T, D)");
@@ -540,11 +568,17 @@ std::vector<at::Tensor> mha_forward(at::Tensor q, at::Tensor k, at::Tensor v,
   int64_t B = q.size(0), NH = q.size(1);
   int T_len = (int)q.size(2), D = (int)q.size(3);
   TORCH_CHECK(D >= 8 && D <= 64 && D % 8 == 0, "head dim must be 8..64, mult of 8");
+  const int* kv_len = lengths_ptr(kv_lengths, q, B, "mha kv_lengths");
+  if (kv_len != nullptr)
+    TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes() &&
+                    k.scalar_type() == q.scalar_type() &&
+                    v.scalar_type() == q.scalar_type(),
+                "mha with kv_lengths: q, k, v must share shape and dtype");
   auto o = at::empty_like(q);
   auto lse = at::empty({B, NH, T_len}, q.options().dtype(at::kFloat));
   dr_mha_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
              lse.data_ptr<float>(), B * NH, T_len, D, (float)scale,
-             is_bf16(q), cur_stream());
+             is_bf16(q), kv_len, (int)NH, cur_stream());
   return {o, lse};
 }
 
@@ -588,10 +622,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("reverse"), py::arg("save"), py::arg("fp8") = false);
   m.def("gru_seq_decode", &gru_seq_decode, py::arg("xg"), py::arg("w_hh"),
         py::arg("b_hh"), py::arg("h0"), py::arg("gamma"), py::arg("beta"),
-        py::arg("wh_fwd"), py::arg("O"), py::arg("reverse"), py::arg("fp8") = false);
+        py::arg("wh_fwd"), py::arg("O"), py::arg("reverse"), py::arg("fp8") = false,
+        py::arg("lengths") = py::none());
   m.def("gru_seq_backward_kernel", &gru_seq_backward_kernel);
   m.def("gru_seq_backward_heads_kernel", &gru_seq_backward_heads_kernel);
   m.def("gru_bwd_reduce", &gru_bwd_reduce);
-  m.def("mha_forward", &mha_forward);
+  m.def("mha_forward", &mha_forward, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("scale"), py::arg("kv_lengths") = py::none());
   m.def("mha_backward", &mha_backward);
 }

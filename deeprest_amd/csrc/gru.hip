@@ -176,7 +176,20 @@ __device__ __forceinline__ bf16x8 ld_frag<float>(const float* src) {
 // 16-wide N-tiles and stores out (B, TT, C, O); the state after the last
 // processed step goes to h_last (B, C, H).  The image sits in LDS as 32 more
 // 256-byte rows behind the W image (8 KB, same swizzle, whatever FP8 is).
-template <typename T, bool SAVE, bool FP8 = false, int NSUB = 1, bool HEADS = false>
+// VARLEN = true (HEADS only): batch b is valid at t < clamp(lens[b], 1, TT).
+// A row whose time index is padding HOLDS its state through a select on
+// hnew — whatever the padded xg holds, NaN included, is computed and thrown
+// away — rewrites the identical rounded value into the h mirror, and stores
+// no head output (out arrives zeroed).  Rows of one wave differ in length,
+// so the predicate is per row; each lane keeps its 4 rows' clamped lengths
+// in registers (the 8-wave variant has no LDS byte left).  The FP8 variant
+// already fills all 512 registers and spills, so its lengths twin streams
+// gamma / beta / b_hh from L1/L2 per step, as the 8-wave variant does,
+// instead of holding them in 120 registers — gamma / beta rounded to bf16 on
+// the way, so the values are the ones the packed registers hold.  h_last is
+// each row's state after its own last valid step.
+template <typename T, bool SAVE, bool FP8 = false, int NSUB = 1, bool HEADS = false,
+          bool VARLEN = false>
 __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     const T* __restrict__ xg,      // (B, TT, 3H)
     const T* __restrict__ gamma,   // (C, 3H)
@@ -190,8 +203,10 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     const uint16_t* __restrict__ wh_fwd,  // HEADS: (32, H) bf16 head weight image
     T* __restrict__ out,           // HEADS: (B, TT, C, O)
     T* __restrict__ h_last,        // HEADS: (B, C, H)
-    int O) {
+    int O,
+    const int* __restrict__ lens) {  // VARLEN: (B,) int32
   static_assert(!(HEADS && SAVE), "the head phase is inference-only");
+  static_assert(HEADS || !VARLEN, "per-row lengths exist in the decode kernel only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ELT = FP8 ? 1 : 2;             // GEMM-tile element bytes
   constexpr int BROWS = ROWS * NSUB;           // rows per block
@@ -200,6 +215,8 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
   char* WHl = smem + G3H * H * ELT;            // (HEADS) 32 x 128 bf16 swizzled
   char* Hl = WHl + (HEADS ? 32 * H * 2 : 0);
   char* XGl = Hl + BROWS * H * ELT;
+  // gamma/beta/b_hh in registers (NSUB == 1) or streamed per step
+  constexpr bool GB_REGS = (NSUB == 1) && !(VARLEN && FP8);
 
   const int tid = threadIdx.x;
   const int wv = tid / DR_WAVE;
@@ -249,19 +266,28 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     b_of[i] = (int)(rr / C);
     comp_of[i] = (int)(rr % C);
   }
+  // VARLEN: this lane's rows' lengths, clamped here so that no value can
+  // index outside [0, TT)
+  int len_of[4];
+  if constexpr (VARLEN) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      len_of[i] = std::min(std::max(lens[b_of[i]], 1), TT);
+    }
+  }
 
   // ---- preload T-invariant per-lane values ----
   // NSUB==1: gamma/beta packed as bf16 pairs in one u32 per (row, gate,
   // tile) — LDS caps this variant at 1 block/CU so the registers are free.
   // NSUB==2: two waves/SIMD need the registers back; gamma/beta/b_hh are
   // L1/L2-resident and reload per step (opaque pointers in the epilogue).
-  constexpr int GBN = (NSUB == 1) ? 8 : 1;
+  constexpr int GBN = GB_REGS ? 8 : 1;
   uint32_t gb[4][3][GBN];
   float bh[3][GBN];
   int gb_off[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) gb_off[i] = comp_of[i] * G3H;
-  if constexpr (NSUB == 1) {
+  if constexpr (GB_REGS) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const T* grow = gamma + gb_off[i];
@@ -381,6 +407,9 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
   int out_toff = 0;                          // HEADS: the same, 32-bit
   const int stage_tstep = (reverse ? -1 : 1) * G3H;
   for (int step = 0; step < TT; ++step) {
+    // VARLEN: row i is active at this step iff t_now < len_of[i]
+    const int t_now = reverse ? (TT - 1 - step) : step;
+    (void)t_now;
     // A-fragments: this wave's 16 rows of the h tile, all 4 K-tiles
     bf16x8 afrag[KT];
     int64_t afrag8[KT];
@@ -432,12 +461,14 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     const T* gm_v = gamma;
     const T* bt_v = beta;
     const float* bh_v = b_hh;
-    if constexpr (NSUB == 2) asm volatile("" : "+v"(gm_v), "+v"(bt_v), "+v"(bh_v));
+    if constexpr (!GB_REGS) asm volatile("" : "+v"(gm_v), "+v"(bt_v), "+v"(bh_v));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const T* grow = gm_v + gb_off[i];
       const T* brow = bt_v + gb_off[i];
       float fr[8], fz[8], fn[8];
+      bool active = true;
+      if constexpr (VARLEN) active = t_now < len_of[i];
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) {
         // pi layout: per-gate values sit at CONSECUTIVE LDS addresses over
@@ -447,25 +478,47 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
         float xn = bf2f(xg_rows[i][2 * H + nt]);
         int col = nt * 16 + c_col;
         float gmr, gmz, gmn, btr, btz, btn, bhr, bhz, bhn;
-        if constexpr (NSUB == 1) {
+        if constexpr (GB_REGS) {
           gmr = bf2f((uint16_t)gb[i][0][nt]); btr = bf2f((uint16_t)(gb[i][0][nt] >> 16));
           gmz = bf2f((uint16_t)gb[i][1][nt]); btz = bf2f((uint16_t)(gb[i][1][nt] >> 16));
           gmn = bf2f((uint16_t)gb[i][2][nt]); btn = bf2f((uint16_t)(gb[i][2][nt] >> 16));
           bhr = bh[0][nt]; bhz = bh[1][nt]; bhn = bh[2][nt];
+        } else if constexpr (NSUB == 1) {
+          // streamed twin of the packed registers: same bf16-rounded values
+          gmr = bf2f(f2bf(ldf(grow + col))); btr = bf2f(f2bf(ldf(brow + col)));
+          gmz = bf2f(f2bf(ldf(grow + H + col)));
+          btz = bf2f(f2bf(ldf(brow + H + col)));
+          gmn = bf2f(f2bf(ldf(grow + 2 * H + col)));
+          btn = bf2f(f2bf(ldf(brow + 2 * H + col)));
+          bhr = bh_v[col]; bhz = bh_v[H + col]; bhn = bh_v[2 * H + col];
         } else {
           gmr = ldf(grow + col); btr = ldf(brow + col);
           gmz = ldf(grow + H + col); btz = ldf(brow + H + col);
           gmn = ldf(grow + 2 * H + col); btn = ldf(brow + 2 * H + col);
           bhr = bh_v[col]; bhz = bh_v[H + col]; bhn = bh_v[2 * H + col];
         }
-        float g_r = xr * gmr + btr;
-        float g_z = xz * gmz + btz;
-        float g_n = xn * gmn + btn;
+        float g_r, g_z, g_n;
+        if constexpr (!GB_REGS && NSUB == 1) {
+          // Pin what -ffp-contract leaves to the compiler, so that this
+          // variant computes bit for bit what its register-held twin does:
+          // there the r and z products are rounded before beta is added
+          // (they pair up with acc + b_hh into packed adds) and only the n
+          // gate is contracted into an FMA; with streamed operands all three
+          // came out as rounded packed multiplies (1 ulp apart in fp32 IO).
+          g_r = __fmul_rn(xr, gmr) + btr;
+          g_z = __fmul_rn(xz, gmz) + btz;
+          g_n = __builtin_fmaf(xn, gmn, btn);
+        } else {
+          g_r = xr * gmr + btr;
+          g_z = xz * gmz + btz;
+          g_n = xn * gmn + btn;
+        }
         float rp = sigmoidf_(acc[nt][i] + bhr + g_r);
         float zp = sigmoidf_(acc[nt + 8][i] + bhz + g_z);
         float hn = acc[nt + 16][i] + bhn;
         float nn = tanhf_(g_n + rp * hn);
         float hnew = (1.f - zp) * nn + zp * h[i][nt];
+        if constexpr (VARLEN) hnew = active ? hnew : h[i][nt];
         h[i][nt] = hnew;
         if constexpr (FP8)
           *reinterpret_cast<uint8_t*>(Hl + swz8(row_of[i], col)) = f2fp8(hnew);
@@ -523,7 +576,8 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
           if (j < O) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-              if (live[i]) stf(out + (out_bc[i] + out_toff) * O + j, a[i]);
+              if (live[i] && (!VARLEN || t_now < len_of[i]))
+                stf(out + (out_bc[i] + out_toff) * O + j, a[i]);
           }
         }
       }
@@ -1060,13 +1114,13 @@ static void gru_fwd_launch_t(const void* xg, const void* gamma, const void* beta
                          dim3(2 * THREADS), LDS_FWD_8W, stream, (const T*)xg,
                          (const T*)gamma, (const T*)beta, (const uint16_t*)w_gemm,
                          b_hh, (const T*)h0, (T*)h_all, (T*)saves, B, TT, C,
-                         reverse, nullptr, nullptr, nullptr, 0);
+                         reverse, nullptr, nullptr, nullptr, 0, nullptr);
     else
       hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 2>), dim3(tiles128),
                          dim3(2 * THREADS), LDS_FWD_8W, stream, (const T*)xg,
                          (const T*)gamma, (const T*)beta, (const uint16_t*)w_gemm,
                          b_hh, (const T*)h0, (T*)h_all, (T*)saves, B, TT, C,
-                         reverse, nullptr, nullptr, nullptr, 0);
+                         reverse, nullptr, nullptr, nullptr, 0, nullptr);
     return;
   }
   if (fp8)
@@ -1074,19 +1128,19 @@ static void gru_fwd_launch_t(const void* xg, const void* gamma, const void* beta
                        LDS_FWD_FP8, stream, (const T*)xg, (const T*)gamma,
                        (const T*)beta, (const uint16_t*)w_gemm, b_hh, (const T*)h0,
                        (T*)h_all, (T*)saves, B, TT, C, reverse, nullptr, nullptr,
-                       nullptr, 0);
+                       nullptr, 0, nullptr);
   else if (save)
     hipLaunchKernelGGL((gru_fwd_kernel<T, true>), dim3(grid), dim3(THREADS),
                        LDS_FWD_TOTAL, stream, (const T*)xg, (const T*)gamma,
                        (const T*)beta, (const uint16_t*)w_gemm, b_hh, (const T*)h0,
                        (T*)h_all, (T*)saves, B, TT, C, reverse, nullptr, nullptr,
-                       nullptr, 0);
+                       nullptr, 0, nullptr);
   else
     hipLaunchKernelGGL((gru_fwd_kernel<T, false>), dim3(grid), dim3(THREADS),
                        LDS_FWD_TOTAL, stream, (const T*)xg, (const T*)gamma,
                        (const T*)beta, (const uint16_t*)w_gemm, b_hh, (const T*)h0,
                        (T*)h_all, (T*)saves, B, TT, C, reverse, nullptr, nullptr,
-                       nullptr, 0);
+                       nullptr, 0, nullptr);
 }
 
 // HEADS decode: same three variants behind the same dispatch conditions as
@@ -1095,51 +1149,58 @@ static void gru_fwd_launch_t(const void* xg, const void* gamma, const void* beta
 // declare).
 constexpr int LDS_WH = 32 * H * 2;  // 8192 B
 
-template <typename T>
+// VARLEN: the per-row-length twins (lens = (B,) int32 on the device), same
+// LDS sizes and the same dispatch conditions.
+template <typename T, bool VARLEN>
 static int gru_decode_launch_t(const void* xg, const void* gamma, const void* beta,
                                const void* w_gemm, const float* b_hh,
                                const void* h0, const void* wh_fwd, void* out,
                                void* h_last, int B, int TT, int C, int O,
-                               int reverse, int fp8, hipStream_t stream) {
+                               int reverse, int fp8, const int* lens,
+                               hipStream_t stream) {
   int64_t R = (int64_t)B * C;
   int grid = (int)((R + ROWS - 1) / ROWS);
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&gru_fwd_kernel<T, false, false, 1, true>),
+        reinterpret_cast<const void*>(
+            &gru_fwd_kernel<T, false, false, 1, true, VARLEN>),
         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_TOTAL + LDS_WH);
     if (e == hipSuccess)
       e = hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&gru_fwd_kernel<T, false, true, 1, true>),
+          reinterpret_cast<const void*>(
+              &gru_fwd_kernel<T, false, true, 1, true, VARLEN>),
           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_FP8 + LDS_WH);
     if (e == hipSuccess)
       e = hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&gru_fwd_kernel<T, false, false, 2, true>),
+          reinterpret_cast<const void*>(
+              &gru_fwd_kernel<T, false, false, 2, true, VARLEN>),
           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_8W + LDS_WH);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
   int tiles128 = (int)((R + 2 * ROWS - 1) / (2 * ROWS));
   if (!fp8 && tiles128 >= 192 && C >= 5)
-    hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 2, true>), dim3(tiles128),
-                       dim3(2 * THREADS), LDS_FWD_8W + LDS_WH, stream,
-                       (const T*)xg, (const T*)gamma, (const T*)beta,
+    hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 2, true, VARLEN>),
+                       dim3(tiles128), dim3(2 * THREADS), LDS_FWD_8W + LDS_WH,
+                       stream, (const T*)xg, (const T*)gamma, (const T*)beta,
                        (const uint16_t*)w_gemm, b_hh, (const T*)h0, nullptr,
                        nullptr, B, TT, C, reverse, (const uint16_t*)wh_fwd,
-                       (T*)out, (T*)h_last, O);
+                       (T*)out, (T*)h_last, O, lens);
   else if (fp8)
-    hipLaunchKernelGGL((gru_fwd_kernel<T, false, true, 1, true>), dim3(grid),
-                       dim3(THREADS), LDS_FWD_FP8 + LDS_WH, stream, (const T*)xg,
-                       (const T*)gamma, (const T*)beta, (const uint16_t*)w_gemm,
-                       b_hh, (const T*)h0, nullptr, nullptr, B, TT, C, reverse,
-                       (const uint16_t*)wh_fwd, (T*)out, (T*)h_last, O);
-  else
-    hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 1, true>), dim3(grid),
-                       dim3(THREADS), LDS_FWD_TOTAL + LDS_WH, stream,
+    hipLaunchKernelGGL((gru_fwd_kernel<T, false, true, 1, true, VARLEN>),
+                       dim3(grid), dim3(THREADS), LDS_FWD_FP8 + LDS_WH, stream,
                        (const T*)xg, (const T*)gamma, (const T*)beta,
                        (const uint16_t*)w_gemm, b_hh, (const T*)h0, nullptr,
                        nullptr, B, TT, C, reverse, (const uint16_t*)wh_fwd,
-                       (T*)out, (T*)h_last, O);
+                       (T*)out, (T*)h_last, O, lens);
+  else
+    hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 1, true, VARLEN>),
+                       dim3(grid), dim3(THREADS), LDS_FWD_TOTAL + LDS_WH, stream,
+                       (const T*)xg, (const T*)gamma, (const T*)beta,
+                       (const uint16_t*)w_gemm, b_hh, (const T*)h0, nullptr,
+                       nullptr, B, TT, C, reverse, (const uint16_t*)wh_fwd,
+                       (T*)out, (T*)h_last, O, lens);
   return (int)hipGetLastError();   // a rejected launch is the caller's error
 }
 
@@ -1232,20 +1293,31 @@ void dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
 }
 
 // Inference decode: GRU sequence + head projection, no h_all.  wh_fwd is the
-// (32, H) bf16 head weight image, rows >= O exact zero.  Returns the HIP
-// error of the attribute setup or the launch (0 = success).
+// (32, H) bf16 head weight image, rows >= O exact zero.  lens == nullptr:
+// every row runs all TT steps; otherwise (B,) int32 per-sample lengths on the
+// device and out must arrive zeroed.  Returns the HIP error of the attribute
+// setup or the launch (0 = success).
 int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
                   const void* w_hh, const float* b_hh, const void* h0,
                   const void* wh_fwd, void* out, void* h_last, int B, int TT,
                   int C, int O, int reverse, int fp8, int is_bf16,
-                  hipStream_t stream) {
+                  const int* lens, hipStream_t stream) {
+  if (lens != nullptr) {
+    if (is_bf16)
+      return dr::gru_decode_launch_t<uint16_t, true>(
+          xg, gamma, beta, w_hh, b_hh, h0, wh_fwd, out, h_last, B, TT, C, O,
+          reverse, fp8, lens, stream);
+    return dr::gru_decode_launch_t<float, true>(xg, gamma, beta, w_hh, b_hh, h0,
+                                                wh_fwd, out, h_last, B, TT, C, O,
+                                                reverse, fp8, lens, stream);
+  }
   if (is_bf16)
-    return dr::gru_decode_launch_t<uint16_t>(xg, gamma, beta, w_hh, b_hh, h0,
-                                             wh_fwd, out, h_last, B, TT, C, O,
-                                             reverse, fp8, stream);
-  return dr::gru_decode_launch_t<float>(xg, gamma, beta, w_hh, b_hh, h0, wh_fwd,
-                                        out, h_last, B, TT, C, O, reverse, fp8,
-                                        stream);
+    return dr::gru_decode_launch_t<uint16_t, false>(
+        xg, gamma, beta, w_hh, b_hh, h0, wh_fwd, out, h_last, B, TT, C, O,
+        reverse, fp8, nullptr, stream);
+  return dr::gru_decode_launch_t<float, false>(xg, gamma, beta, w_hh, b_hh, h0,
+                                               wh_fwd, out, h_last, B, TT, C, O,
+                                               reverse, fp8, nullptr, stream);
 }
 
 // wh_img == nullptr: grad is grad_h (B, TT, C, H), the unfused path.

@@ -191,6 +191,14 @@ class _LayerNormOp(nn.Module):
         return layer_norm(x, self.weight, self.bias, self.eps)
 
 
+def _mha(q, k, v, kv_lengths):
+    """mha_forward; the lengths argument is passed only when there is one, so
+    the fixed-length call is the one it always was."""
+    if kv_lengths is None:
+        return mha_forward(q, k, v)
+    return mha_forward(q, k, v, kv_lengths=kv_lengths)
+
+
 class _EncoderLayer(nn.Module):
     def __init__(self, cfg: DeepRestNetConfig) -> None:
         super().__init__()
@@ -205,12 +213,13 @@ class _EncoderLayer(nn.Module):
         self.n_heads = cfg.n_heads
         self.dropout = nn.Dropout(cfg.dropout)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor,
+                kv_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, T, D = x.shape
         h = self.ln1(x)
         qkv = self.qkv(h).view(B, T, 3, self.n_heads, D // self.n_heads)
         q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # (B,h,T,dh)
-        attn = mha_forward(q, k, v)
+        attn = _mha(q, k, v, kv_lengths)
         attn = attn.transpose(1, 2).reshape(B, T, D)
         x = x + self.dropout(self.proj(attn))
         h = self.ln2(x)
@@ -218,7 +227,8 @@ class _EncoderLayer(nn.Module):
         return x
 
     def forward_fused(self, x: torch.Tensor, h: torch.Tensor,
-                      next_ln: Optional[_LayerNormOp]):
+                      next_ln: Optional[_LayerNormOp],
+                      kv_lengths: Optional[torch.Tensor] = None):
         """Same math with the residual glue fused: takes the residual stream
         ``x`` and ``h = ln1(x)``; the FFN residual add is fused with the NEXT
         layer's ln1 (``next_ln``; None for the last layer).  Returns
@@ -227,7 +237,7 @@ class _EncoderLayer(nn.Module):
         p, training = self.dropout.p, self.training
         qkv = self.qkv(h).view(B, T, 3, self.n_heads, D // self.n_heads)
         q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # (B,h,T,dh)
-        attn = mha_forward(q, k, v)
+        attn = _mha(q, k, v, kv_lengths)
         attn = attn.transpose(1, 2).reshape(B, T, D)
         x, h = dropout_add_layer_norm(self.proj(attn), x, self.ln2.weight,
                                       self.ln2.bias, p, training, self.ln2.eps)
@@ -348,10 +358,11 @@ class _GRUDecoderBank(nn.Module):
 
     def decode_heads(self, enc: torch.Tensor, comp: torch.Tensor,
                      w_heads: Sequence[torch.Tensor], fp8: bool = False,
-                     d: int = 0):
+                     d: int = 0, lengths: Optional[torch.Tensor] = None):
         """Inference decode of direction ``d`` (ops.fused_gru_decode):
         returns ``(part (B, T, C, O), h_last (B, C, H))`` with ``part`` that
-        direction's head output; the hidden sequence is never materialized."""
+        direction's head output; the hidden sequence is never materialized.
+        ``lengths`` (B,) int32: per-sample window lengths, see the op."""
         B = enc.shape[0]
         C = comp.shape[0]
         sfx = "_r" if d else ""
@@ -360,9 +371,14 @@ class _GRUDecoderBank(nn.Module):
         beta = getattr(self, "cond_beta" + sfx)(comp)
         h0 = torch.tanh(getattr(self, "h0_proj" + sfx)(comp))
         h0 = h0.unsqueeze(0).expand(B, C, self.hidden).contiguous()
+        if lengths is None:
+            return fused_gru_decode(xg, getattr(self, "w_hh" + sfx),
+                                    getattr(self, "b_hh" + sfx), h0, gamma, beta,
+                                    w_heads[d], reverse=bool(d), fp8=fp8)
         return fused_gru_decode(xg, getattr(self, "w_hh" + sfx),
                                 getattr(self, "b_hh" + sfx), h0, gamma, beta,
-                                w_heads[d], reverse=bool(d), fp8=fp8)
+                                w_heads[d], reverse=bool(d), fp8=fp8,
+                                lengths=lengths)
 
 
 # -------------------------------------------------------------------- model
@@ -421,8 +437,19 @@ class DeepRestNet(nn.Module):
         self._pos_cache = pe
         return pe.to(dtype)
 
-    def forward(self, traffic: torch.Tensor) -> torch.Tensor:
-        """traffic: (B, T, P) normalized call-path counts -> (B, T, M, Q)."""
+    def forward(self, traffic: torch.Tensor,
+                lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """traffic: (B, T, P) normalized call-path counts -> (B, T, M, Q).
+
+        ``lengths`` (B,) int32 on traffic's device (inference only: eval
+        mode, grad disabled): sample b is the window traffic[b, :lengths[b]]
+        and everything behind it is padding.  ``out[b, :L]`` is what the
+        model returns for that window alone, nothing stored in the padding
+        can reach it, and ``out[b, L:]`` is exact zero.  The lengths are
+        read on the device only, so a captured graph stays valid when the
+        buffer is rewritten between replays."""
+        if lengths is not None:
+            return self._forward_lengths(traffic, lengths)
         B, T, P = traffic.shape
         x = self.in_proj(traffic)
         x = x + self._pos_encoding(T, x.device, x.dtype)
@@ -451,6 +478,47 @@ class DeepRestNet(nn.Module):
             return self._finish_heads(self.decoder.forward_heads(x, comp, w_dirs))
         h_dirs = self.decoder(x, comp, fp8=fp8)               # tuple of (B,T,C,H)
         return self._apply_heads(h_dirs)
+
+    def _forward_lengths(self, traffic: torch.Tensor,
+                         lengths: torch.Tensor) -> torch.Tensor:
+        """forward() for windows of per-sample length.  Every stage but two
+        is per-position; attention masks the padded keys and the decoders
+        run each sample's own steps (both inside their kernels on GPU)."""
+        if self.training or torch.is_grad_enabled():
+            raise ValueError(
+                "lengths are inference-only: call model.eval() and run under "
+                "torch.no_grad()")
+        B, T, P = traffic.shape
+        if lengths.dim() != 1 or lengths.shape[0] != B:
+            raise ValueError(
+                f"lengths must be ({B},), got {tuple(lengths.shape)}")
+        lengths = lengths.to(device=traffic.device, dtype=torch.int32)
+        x = self.in_proj(traffic)
+        x = x + self._pos_encoding(T, x.device, x.dtype)
+        x = self.in_norm(x)
+        if self.cfg.fused_residual_norm:
+            x = self._encode_fused(x, lengths)
+        else:
+            for layer in self.layers:
+                x = layer(x, lengths)
+        comp = self.graph()                                   # (C, comp_dim)
+        fp8 = bool(self.cfg.fp8_inference and traffic.is_cuda)
+        # always the decode op, whatever cfg.fused_head_decode says: it is
+        # the GRU entry that knows about lengths (native kernel on GPU when
+        # the shape fits it, the composed reference otherwise)
+        w_dirs = self._head_weights_per_dir()
+        out = None
+        for d in range(len(w_dirs)):
+            part, _ = self.decoder.decode_heads(x, comp, w_dirs, fp8, d,
+                                                lengths=lengths)
+            out = part if out is None else out + part
+        preds = self._finish_heads(out)
+        # metric_bias made the padded positions non-zero: zero them by select
+        valid = (torch.arange(T, device=preds.device)[None, :]
+                 < lengths.clamp(1, T)[:, None])
+        return torch.where(valid[:, :, None, None], preds,
+                           torch.zeros((), dtype=preds.dtype,
+                                       device=preds.device))
 
     def _use_fused_heads(self, enc: torch.Tensor, comp: torch.Tensor,
                          fp8: bool) -> bool:
@@ -483,7 +551,8 @@ class DeepRestNet(nn.Module):
         dirs = 2 if self.cfg.bidirectional else 1
         return [w_all[:, d * H : (d + 1) * H].contiguous() for d in range(dirs)]
 
-    def _encode_fused(self, x: torch.Tensor) -> torch.Tensor:
+    def _encode_fused(self, x: torch.Tensor,
+                      kv_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Encoder stack with cfg.fused_residual_norm: carries the residual
         stream ``x`` and the normed tensor ``h`` the next sub-block consumes,
         so every ``x + dropout(branch)`` and the LayerNorm after it are one
@@ -495,7 +564,10 @@ class DeepRestNet(nn.Module):
         h = self.layers[0].ln1(x)
         for i, layer in enumerate(self.layers):
             next_ln = self.layers[i + 1].ln1 if i + 1 < n else None
-            x, h = layer.forward_fused(x, h, next_ln)
+            if kv_lengths is None:
+                x, h = layer.forward_fused(x, h, next_ln)
+            else:
+                x, h = layer.forward_fused(x, h, next_ln, kv_lengths)
         return x
 
     def _apply_heads(self, h_dirs) -> torch.Tensor:

@@ -30,13 +30,31 @@ from .native import require_native
 
 
 def reference_mha(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                  scale: Optional[float] = None) -> torch.Tensor:
-    """q,k,v: (B, H, T, D). Plain composition (the numerics oracle)."""
+                  scale: Optional[float] = None,
+                  kv_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q,k,v: (B, H, T, D). Plain composition (the numerics oracle).
+
+    ``kv_lengths`` (B,) int: sample b is valid at t < clamp(kv_lengths[b], 1,
+    T).  Padded keys are absent (-inf before the softmax), padded q/k/v
+    values are replaced by zero through a select before any arithmetic (a NaN
+    there cannot reach a valid row), and output rows at or past the length
+    are exact zeros.  Broadcasting only: no host read of the lengths."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if kv_lengths is None:
+        s = torch.matmul(q, k.transpose(-1, -2)) * scale
+        p = torch.softmax(s.float(), dim=-1).to(q.dtype)
+        return torch.matmul(p, v)
+    T = q.shape[2]
+    L = kv_lengths.to(q.device).clamp(1, T)
+    valid = torch.arange(T, device=q.device)[None, :] < L[:, None]     # (B, T)
+    row = valid[:, None, :, None]                                      # (B,1,T,1)
+    zero = torch.zeros((), dtype=q.dtype, device=q.device)
+    q, k, v = (torch.where(row, t, zero) for t in (q, k, v))
     s = torch.matmul(q, k.transpose(-1, -2)) * scale
-    p = torch.softmax(s.float(), dim=-1).to(q.dtype)
-    return torch.matmul(p, v)
+    s = s.float().masked_fill(~valid[:, None, None, :], float("-inf"))
+    p = torch.softmax(s, dim=-1).to(q.dtype)
+    return torch.where(row, torch.matmul(p, v), zero)
 
 
 class _MHAFunction(torch.autograd.Function):
@@ -58,10 +76,26 @@ class _MHAFunction(torch.autograd.Function):
 
 
 def mha_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                scale: Optional[float] = None) -> torch.Tensor:
-    """Fused attention forward; q,k,v: (B, H, T, D) contiguous."""
+                scale: Optional[float] = None,
+                kv_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Fused attention forward; q,k,v: (B, H, T, D) contiguous.
+
+    ``kv_lengths`` (B,) int32 on the inputs' device: per-sample valid
+    lengths (see ``reference_mha``).  Inference only — the kernel is called
+    outside the autograd node and the call raises when grad mode is on and
+    an input requires grad.  The lengths are read on the device."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if kv_lengths is not None:
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+            raise RuntimeError(
+                "mha_forward with kv_lengths is inference-only (no autograd)")
+        if q.is_cuda:
+            ext = require_native("mha_forward")
+            o, _ = ext.mha_forward(q.contiguous(), k.contiguous(),
+                                   v.contiguous(), float(scale), kv_lengths)
+            return o
+        return reference_mha(q, k, v, scale, kv_lengths)
     if q.is_cuda:
         return _MHAFunction.apply(q.contiguous(), k.contiguous(), v.contiguous(), scale)
     return reference_mha(q, k, v, scale)

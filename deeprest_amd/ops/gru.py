@@ -67,13 +67,24 @@ def reference_gru_sequence(
     gamma: Optional[torch.Tensor] = None,  # (C, 3H) FiLM scale
     beta: Optional[torch.Tensor] = None,   # (C, 3H) FiLM shift
     reverse: bool = False,
-) -> torch.Tensor:
-    """Differentiable PyTorch composition; returns h_all (B, T, C, H)."""
+    lengths: Optional[torch.Tensor] = None,   # (B,) int per-sample lengths
+    return_state: bool = False,
+):
+    """Differentiable PyTorch composition; returns h_all (B, T, C, H).
+
+    ``lengths``: sample b is valid at t < clamp(lengths[b], 1, T).  At a
+    padded step the sample HOLDS its state through ``torch.where`` (whatever
+    the padded x_gates hold, NaN included, is computed and discarded) and
+    its h_all entry is zero; so the reverse direction starts from h0 at each
+    sample's own last step.  ``return_state=True`` returns ``(h_all, h)``
+    with ``h`` the final held state (B, C, H)."""
     B, T, G = x_gates.shape
     _, C, H = h0.shape
     assert G == 3 * H, f"x_gates last dim {G} != 3*H ({3 * H})"
     h = h0
     outs = []
+    if lengths is not None:
+        lengths = lengths.to(x_gates.device).clamp(1, T)
     steps = range(T - 1, -1, -1) if reverse else range(T)
     w_hh_t = w_hh.t()  # (H, 3H)
     for t in steps:
@@ -86,11 +97,18 @@ def reference_gru_sequence(
         r = torch.sigmoid(g[..., :H] + hh[..., :H])
         z = torch.sigmoid(g[..., H : 2 * H] + hh[..., H : 2 * H])
         n = torch.tanh(g[..., 2 * H :] + r * hh[..., 2 * H :])
-        h = (1.0 - z) * n + z * h
-        outs.append(h)
+        h_new = (1.0 - z) * n + z * h
+        if lengths is None:
+            h = h_new
+            outs.append(h)
+        else:
+            active = (lengths > t)[:, None, None]       # (B, 1, 1), on device
+            h = torch.where(active, h_new, h)
+            outs.append(torch.where(active, h_new, torch.zeros_like(h_new)))
     if reverse:
         outs.reverse()
-    return torch.stack(outs, dim=1)                     # (B, T, C, H)
+    h_all = torch.stack(outs, dim=1)                    # (B, T, C, H)
+    return (h_all, h) if return_state else h_all
 
 
 class _FusedGRUSequence(torch.autograd.Function):
@@ -357,6 +375,7 @@ def fused_gru_decode(
     w_head: torch.Tensor,        # (O, H) head weights of this direction
     reverse: bool = False,
     fp8: bool = False,
+    lengths: Optional[torch.Tensor] = None,   # (B,) int32 per-sample lengths
 ):
     """Inference decode: ``(F.linear(h_all, w_head), h_all[:, last])`` with
     ``h_all = fused_gru_sequence(...)`` -> ``out (B, T, C, O)`` and ``h_last
@@ -367,7 +386,15 @@ def fused_gru_decode(
     projection runs per step inside the GRU kernel and ``h_all`` is never
     materialized.  Everywhere else (CPU, off-spec shapes, wider heads) it is
     the composition of the two ops.  Not differentiable: raises when grad
-    mode is on and an input requires grad."""
+    mode is on and an input requires grad.
+
+    ``lengths`` (B,) int32 on the inputs' device, read there (no host sync):
+    sample b runs its own steps t < clamp(lengths[b], 1, T) only — forward
+    0..L-1, reverse L-1..0, both from h0.  ``out`` is exact zero at padded
+    positions, nothing stored in padded x_gates can reach a valid output, and
+    ``h_last`` is each sample's state after its own last valid step.  The
+    composed path then goes through ``reference_gru_sequence`` (the plain
+    sequence kernel does not know about lengths; fp8 does not apply)."""
     if torch.is_grad_enabled() and any(
         t.requires_grad
         for t in (x_gates, w_hh, b_hh, h0, gamma, beta, w_head)
@@ -376,6 +403,13 @@ def fused_gru_decode(
     O = w_head.shape[0]
     native = (x_gates.is_cuda and gru_kernel_supports(h0.shape[2], h0.shape[1])
               and O <= HEAD_FUSE_MAX_OUT)
+    if not native and lengths is not None:
+        h_all, h_last = reference_gru_sequence(
+            x_gates, w_hh, b_hh, h0, gamma, beta, reverse, lengths=lengths,
+            return_state=True)
+        # padded h_all rows are zero and the heads have no bias: out is too
+        out = torch.nn.functional.linear(h_all, w_head.to(h_all.dtype))
+        return out, h_last
     if not native:
         h_all = fused_gru_sequence(x_gates, w_hh, b_hh, h0, gamma, beta,
                                    reverse, fp8=fp8)
@@ -394,6 +428,6 @@ def fused_gru_decode(
         h0.to(dt).contiguous(),
         gamma.to(dt).contiguous(),
         beta.to(dt).contiguous(),
-        wh_fwd, O, bool(reverse), bool(fp8),
+        wh_fwd, O, bool(reverse), bool(fp8), lengths,
     )
     return out, h_last

@@ -9,6 +9,13 @@ HTTP requests naturally meet here.
 Policy: a batch flushes when the pending window count reaches
 ``max_batch`` or ``max_wait_ms`` after the first request arrived —
 the classic latency/throughput knob.
+
+Window lengths: a predictor built with ``max_window`` serves requests of
+different window lengths from one call — a flush pads every request to the
+batch's largest T, passes the per-window lengths along, and trims each
+caller's slice back to its own T.  A request longer than ``max_window``
+fails alone, when it is enqueued.  Predictors without ``max_window`` are
+served exactly as before (one shared T per flush).
 """
 
 from __future__ import annotations
@@ -56,9 +63,30 @@ class MicroBatcher:
         with self._run_lock:
             self._run_locked(batch)
 
+    def _predict_mixed(self, batch: List[tuple]) -> Dict[str, np.ndarray]:
+        """One predictor call for requests of different window lengths:
+        pad to the largest T (on the requests' device), pass the lengths."""
+        ws = [w if isinstance(w, torch.Tensor)
+              else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+              for w, _, _ in batch]
+        T = max(int(w.shape[1]) for w in ws)
+        n = sum(int(w.shape[0]) for w in ws)
+        x = ws[0].new_zeros((n, T, ws[0].shape[2]))
+        lens: List[int] = []
+        s = 0
+        for w in ws:
+            x[s : s + w.shape[0], : w.shape[1]] = w
+            lens += [int(w.shape[1])] * int(w.shape[0])
+            s += int(w.shape[0])
+        lengths = torch.tensor(lens, dtype=torch.int32, device=x.device)
+        return self.predictor.predict_tensor(x, lengths)
+
     def _run_locked(self, batch: List[tuple]) -> None:
+        mixed = getattr(self.predictor, "max_window", None) is not None
         try:
-            if isinstance(batch[0][0], torch.Tensor):
+            if mixed:
+                out = self._predict_mixed(batch)
+            elif isinstance(batch[0][0], torch.Tensor):
                 # device tensors (each client thread already did its H2D):
                 # concatenate ON DEVICE and take the tensor fast path
                 out = self.predictor.predict_tensor(
@@ -73,7 +101,10 @@ class MicroBatcher:
         s = 0
         for w, ev, slot in batch:
             n = len(w)
-            if err is None:
+            if err is None and mixed:
+                slot["out"] = {k: v[s : s + n, : w.shape[1]]
+                               for k, v in out.items()}
+            elif err is None:
                 slot["out"] = {k: v[s : s + n] for k, v in out.items()}
             else:
                 slot["err"] = err
@@ -90,6 +121,12 @@ class MicroBatcher:
         its own H2D copy up front (releases the GIL) so enqueue cost
         parallelizes across client threads and the flush is one device-side
         concat + one graph replay."""
+        max_window = getattr(self.predictor, "max_window", None)
+        if max_window is not None:
+            T = np.shape(traffic_windows)[1]
+            if T > max_window:         # fails alone, before it joins a batch
+                raise ValueError(
+                    f"window length {T} exceeds max_window {max_window}")
         if hasattr(self.predictor, "predict_tensor"):
             x = np.ascontiguousarray(np.asarray(traffic_windows),
                                      dtype=np.float32)

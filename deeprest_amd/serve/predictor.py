@@ -15,6 +15,14 @@ tensors) — no intermediate device tensor, so bulk 1k-window inference is a
 single copy + one replay, which beats the eager path (round 1's single
 64-window graph lost at bulk sizes because 1k windows took 16 chunked
 replays; measured in profiles/r02_serve_p50.md).
+
+Variable-length windows (``max_window``): without it every distinct window
+length T captures its own graph per batch tier.  With ``max_window=W`` there
+is ONE graph per tier, captured over a ``(tier, W, P)`` input buffer and a
+``(tier,)`` int32 lengths buffer the model reads on the device; a request of
+any T <= W — or a ragged mix of lengths — is copied into the buffer's
+``[:n, :T]`` corner, its lengths are written, and the same graph replays.
+Padded positions come back as NaN.  Measured in profiles/r06_varlen.md.
 """
 
 from __future__ import annotations
@@ -48,7 +56,12 @@ class Predictor:
         residual_ridge: Optional[np.ndarray] = None,   # (P+1, M): the net's
         # outputs are residuals over this ridge (train.residual_base)
         conformal: Optional[np.ndarray] = None,        # (M,) CQR band widening
+        max_window: Optional[int] = None,     # serve any T <= max_window (and
+        # ragged batches) from one graph per tier; None: one graph per (tier, T)
     ) -> None:
+        if max_window is not None and int(max_window) < 1:
+            raise ValueError(f"max_window must be >= 1, got {max_window}")
+        self.max_window = int(max_window) if max_window is not None else None
         self.target_transform = target_transform
         self.residual_ridge = (np.asarray(residual_ridge)
                                if residual_ridge is not None else None)
@@ -68,7 +81,10 @@ class Predictor:
             graph_batches = (graph_batch,) if graph_batch else DEFAULT_GRAPH_BATCHES
         self.graph_batches: Tuple[int, ...] = tuple(sorted(set(graph_batches)))
         self.use_graph = use_graph and self.device.type == "cuda"
-        # (batch, T) -> (graph, input buffer, output buffer)
+        # (batch, T) -> (graph, input buffer, output buffer, lengths buffer);
+        # with max_window the key is (batch, max_window) and the lengths
+        # buffer is the (batch,) int32 tensor the captured forward reads,
+        # otherwise it is None
         self._graphs: Dict[Tuple[int, int], tuple] = {}
 
     @staticmethod
@@ -93,27 +109,49 @@ class Predictor:
         return sorted({b for (b, _t) in self._graphs})
 
     # ---------------------------------------------------------------- capture
+    def _tier(self, n: int) -> int:
+        """Smallest configured graph batch >= n."""
+        for bb in self.graph_batches:
+            if bb >= n:
+                return bb
+        raise ValueError(
+            f"batch of {n} windows exceeds the largest configured graph "
+            f"batch {self.graph_batches[-1]}")
+
+    def _check_window(self, T: int) -> None:
+        if self.max_window is not None and T > self.max_window:
+            raise ValueError(
+                f"window length {T} exceeds max_window {self.max_window}")
+
     def _graph_for(self, n: int, T: int, P: int) -> tuple:
-        """Smallest configured graph batch >= n (n must be <= max batch)."""
-        b = next(bb for bb in self.graph_batches if bb >= n)
-        key = (b, T)
+        """Graph of the smallest configured batch >= n: for windows of length
+        T, or — with max_window — the one graph of that tier, which serves
+        every T <= max_window."""
+        b = self._tier(n)
+        self._check_window(T)
+        varlen = self.max_window is not None
+        key = (b, self.max_window if varlen else T)
         got = self._graphs.get(key)
         if got is not None:
             return got
-        gin = torch.zeros(b, T, P, device=self.device)
+        gin = torch.zeros(b, key[1], P, device=self.device)
+        glen = (torch.ones(b, dtype=torch.int32, device=self.device)
+                if varlen else None)
+        run = (lambda: self.model(gin, glen)) if varlen else (
+            lambda: self.model(gin))
         # warmup on a side stream (required before capture)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):
                 with torch.no_grad():
-                    self.model(gin)
+                    run()
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):
             with torch.no_grad():
-                gout = self.model(gin)
-        got = (g, gin, gout)
+                gout = run()
+        got = (g, gin, gout, glen)
         self._graphs[key] = got
         return got
 
@@ -124,43 +162,74 @@ class Predictor:
         Streamed ingestion writes normalized windows directly here (no
         intermediate tensor), then calls ``predict_staged(n)`` — the
         whole-request cost is one replay."""
-        _, gin, _ = self._graph_for(n, T, P)
-        return gin[:n]
+        _, gin, _, _ = self._graph_for(n, T, P)
+        return gin[:n, :T]
 
     @torch.no_grad()
     def predict_staged(self, n: int, T: int) -> torch.Tensor:
         """Replay the graph whose staging buffer was filled with n windows."""
-        b = next(bb for bb in self.graph_batches if bb >= n)
-        g, gin, gout = self._graphs[(b, T)]
+        b = self._tier(n)
+        self._check_window(T)
+        g, gin, gout, glen = self._graphs[
+            (b, T if self.max_window is None else self.max_window)]
         if n < b:
             gin[n:].zero_()
+        if glen is not None:
+            glen[:n].fill_(T)
+            glen[n:].fill_(1)
         g.replay()
-        return gout[:n]
+        return gout[:n, :T]
 
     # ---------------------------------------------------------------- predict
     @torch.no_grad()
-    def predict_normalized(self, x: torch.Tensor) -> torch.Tensor:
+    def predict_normalized(self, x: torch.Tensor,
+                           lengths: Optional[torch.Tensor] = None
+                           ) -> torch.Tensor:
         """x: (N, T, P) normalized traffic -> (N, T, M, Q).
 
         Requests up to the largest configured graph batch are one padded
         replay; larger requests chunk at the largest batch (a 4096-window
         request = four 1024-replays).  CPU inputs are copied H2D straight
-        into the staging buffer."""
+        into the staging buffer.
+
+        With ``max_window``: ``lengths`` (N,) gives each window's own length
+        (default: all T); the output is exact zero at padded positions.  The
+        lengths travel to the model as a device tensor and are never read
+        back on the host."""
         x = x.float()
         N, T, P = x.shape
-        if not self.use_graph:
-            return self.model(x.to(self.device))
+        if self.max_window is None:
+            if lengths is not None:
+                raise ValueError("lengths need a Predictor built with max_window")
+            if not self.use_graph:
+                return self.model(x.to(self.device))
+        else:
+            self._check_window(T)
+            if lengths is None:
+                lengths = torch.full((N,), T, dtype=torch.int32,
+                                     device=self.device)
+            else:
+                lengths = torch.as_tensor(lengths).to(
+                    device=self.device, dtype=torch.int32).reshape(-1)
+                if lengths.shape[0] != N:
+                    raise ValueError(
+                        f"lengths must have {N} entries, got {lengths.shape[0]}")
+            if not self.use_graph:
+                return self.model(x.to(self.device), lengths)
         bmax = self.graph_batches[-1]
         outs = []
         s = 0
         while s < N:
             n = min(N - s, bmax)
-            g, gin, gout = self._graph_for(n, T, P)
-            gin[:n].copy_(x[s : s + n])
+            g, gin, gout, glen = self._graph_for(n, T, P)
+            gin[:n, :T].copy_(x[s : s + n])
             if n < gin.shape[0]:
                 gin[n:].zero_()
+            if glen is not None:
+                glen[:n].copy_(lengths[s : s + n])
+                glen[n:].fill_(1)
             g.replay()
-            outs.append(gout[:n].clone())
+            outs.append(gout[:n, :T].clone())
             s += n
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
@@ -177,13 +246,22 @@ class Predictor:
         return self.predict_tensor(torch.from_numpy(x).to(self.device))
 
     @torch.no_grad()
-    def predict_tensor(self, xt: torch.Tensor) -> Dict[str, np.ndarray]:
+    def predict_tensor(self, xt: torch.Tensor,
+                       lengths: Optional[torch.Tensor] = None
+                       ) -> Dict[str, np.ndarray]:
         """Raw count windows already on device as f32 (N, T, P) — the
         zero-extra-copy entry the micro-batcher uses (client threads do
-        their own H2D, the batch concatenates on device)."""
+        their own H2D, the batch concatenates on device).
+
+        ``lengths`` (N,), with ``max_window`` only: window i is
+        ``xt[i, :lengths[i]]``; the returned arrays are NaN at its padded
+        positions (a denormalized zero would look like a prediction)."""
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(
+                device=xt.device, dtype=torch.int32).reshape(-1)
         if self.x_scaler.scale != 0.0:
             xt = (xt - self.x_scaler.min_val) * (1.0 / self.x_scaler.scale)
-        out = self.predict_normalized(xt).float()
+        out = self.predict_normalized(xt, lengths).float()
         if self.residual_ridge is not None:
             if (self._ridge_t is None
                     or self._ridge_t.device != out.device):
@@ -208,14 +286,48 @@ class Predictor:
             c = self._conformal_t
             out[..., 0] = torch.minimum(out[..., 0] - c, out[..., 1])
             out[..., -1] = torch.maximum(out[..., -1] + c, out[..., -2])
+        pad = None
+        if lengths is not None:
+            T = out.shape[1]
+            pad = (torch.arange(T, device=out.device)[None, :]
+                   >= lengths.to(out.device).clamp(1, T)[:, None]).cpu().numpy()
         out = out.cpu().numpy()                     # (N, T, M, Q)
         preds = {}
         for m, name in enumerate(self.metric_names):
             v = self.y_scalers[m].inverse_transform(out[:, :, m, :])
             if self.target_transform == "log1p":
                 v = np.expm1(v)
-            preds[name] = np.maximum(v, 1e-6)
+            v = np.maximum(v, 1e-6)
+            if pad is not None:
+                v = np.array(v, dtype=np.result_type(v.dtype, np.float32))
+                v[pad] = np.nan
+            preds[name] = v
         return preds
+
+    def predict_ragged(self, windows: Sequence[np.ndarray]
+                       ) -> List[Dict[str, np.ndarray]]:
+        """Windows of different lengths, each (T_i, P) raw call-path counts,
+        served as one padded batch -> one ``{metric: (T_i, Q)}`` per window.
+        Needs ``max_window`` (every T_i <= max_window)."""
+        if self.max_window is None:
+            raise ValueError("predict_ragged needs a Predictor built with max_window")
+        if len(windows) == 0:
+            return []
+        arrs = [np.asarray(w, dtype=np.float32) for w in windows]
+        lens = [int(a.shape[0]) for a in arrs]
+        for a in arrs:
+            if a.ndim != 2 or a.shape[1] != arrs[0].shape[1] or a.shape[0] < 1:
+                raise ValueError("each window must be (T_i >= 1, P) with one P")
+        T = max(lens)
+        self._check_window(T)
+        x = np.zeros((len(arrs), T, arrs[0].shape[1]), dtype=np.float32)
+        for i, a in enumerate(arrs):
+            x[i, : lens[i]] = a
+        out = self.predict_tensor(
+            torch.from_numpy(x).to(self.device),
+            torch.tensor(lens, dtype=torch.int32, device=self.device))
+        return [{k: v[i, : lens[i]] for k, v in out.items()}
+                for i in range(len(arrs))]
 
     def predict_what_if(self, synthesizer, traffic_plan, step_size: int,
                         rng=None) -> Dict[str, np.ndarray]:
