@@ -43,25 +43,27 @@ void dr_fused_adam_dev(const int64_t* meta, int nt, int64_t total,
                        const float* lr_ptr, float beta1, float beta2, float eps,
                        float weight_decay, const int* step_ptr,
                        hipStream_t stream);
-void dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
-                const void* w_hh, const float* b_hh, const void* h0, void* h_all,
-                void* saves, int B, int TT, int C, int reverse, int save,
-                int fp8, int is_bf16, hipStream_t stream);
+// the dr_gru_* entries return the HIP error of their set-up or launches, 0 on
+// success (gru_launch_check below)
+int dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
+               const void* w_hh, const float* b_hh, const void* h0, void* h_all,
+               void* saves, int B, int TT, int C, int reverse, int save,
+               int fp8, int is_bf16, hipStream_t stream);
 int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
                   const void* w_hh, const float* b_hh, const void* h0,
                   const void* wh_fwd, void* out, void* h_last, int B, int TT,
                   int C, int O, int reverse, int fp8, int is_bf16,
                   const int* lens, hipStream_t stream);
-void dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
-                const void* w_fwd, const void* xg, const void* gamma,
-                const void* beta, const float* b_hh, const void* h0,
-                const void* h_all, const void* saves, void* dpre, float* dh0,
-                int B, int TT, int C, int reverse, int is_bf16,
-                hipStream_t stream);
-void dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
-                       void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
-                       void* xg_pi, int64_t BT, int C, int is_bf16,
-                       hipStream_t stream);
+int dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
+               const void* w_fwd, const void* xg, const void* gamma,
+               const void* beta, const float* b_hh, const void* h0,
+               const void* h_all, const void* saves, void* dpre, float* dh0,
+               int B, int TT, int C, int reverse, int is_bf16,
+               hipStream_t stream);
+int dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
+                      void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
+                      void* xg_pi, int64_t BT, int C, int is_bf16,
+                      hipStream_t stream);
 void dr_mha_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                 int64_t BH, int T_len, int D, float scale, int is_bf16,
                 const int* kv_len, int n_heads, hipStream_t stream);
@@ -355,11 +357,26 @@ void fused_adam_capturable(at::Tensor meta_dev, int64_t nt, int64_t total,
 }
 
 // -------------------------------------------------------------------- gru
+// a kernel entry's return value: a rejected set-up or launch is the caller's
+// error, never a silently wrong result
+static void gru_launch_check(int err, const char* what) {
+  TORCH_CHECK(err == 0, what, " kernel launch failed (HIP error ", err, ": ",
+              hipGetErrorString((hipError_t)err), ")");
+}
+
+// the GEMM streams a bf16 weight image from L2 whatever the IO dtype is
+static at::Tensor gru_w_gemm(const at::Tensor& w_hh) {
+  return is_bf16(w_hh) ? w_hh : w_hh.to(at::kBFloat16);
+}
+
 // operand checks shared by the forward entries
 static void gru_forward_checks(const at::Tensor& xg, const at::Tensor& w_hh,
                                const at::Tensor& b_hh, const at::Tensor& h0,
                                const at::Tensor& gamma, const at::Tensor& beta) {
   check_dtype(xg, "x_gates");
+  for (const at::Tensor* t : {&xg, &w_hh, &b_hh, &h0, &gamma, &beta})
+    TORCH_CHECK(t->is_cuda() && t->device() == xg.device(),
+                "gru operands must all be on x_gates' GPU");
   TORCH_CHECK(xg.dim() == 3, "x_gates must be (B, T, 3H)");
   TORCH_CHECK(h0.dim() == 3, "h0 must be (B, C, H)");
   int C = (int)h0.size(1), H = (int)h0.size(2);
@@ -367,6 +384,9 @@ static void gru_forward_checks(const at::Tensor& xg, const at::Tensor& w_hh,
   TORCH_CHECK(C >= 3, "fused GRU kernel requires >= 3 components, got ", C);
   TORCH_CHECK(xg.size(2) == 3 * H && w_hh.size(0) == 3 * H && w_hh.size(1) == H);
   TORCH_CHECK(gamma.sizes() == at::IntArrayRef({C, 3 * H}));
+  TORCH_CHECK(h0.size(0) == xg.size(0) && beta.sizes() == gamma.sizes() &&
+                  b_hh.numel() == 3 * H,
+              "gru operand shapes do not match x_gates (B, T, 3H)");
   TORCH_CHECK(b_hh.scalar_type() == at::kFloat, "b_hh must be f32");
   auto dt = xg.scalar_type();
   TORCH_CHECK(w_hh.scalar_type() == dt && h0.scalar_type() == dt &&
@@ -374,7 +394,6 @@ static void gru_forward_checks(const at::Tensor& xg, const at::Tensor& w_hh,
               "gru operand dtypes must match x_gates");
   TORCH_CHECK(xg.is_contiguous() && w_hh.is_contiguous() && h0.is_contiguous() &&
               gamma.is_contiguous() && beta.is_contiguous() && b_hh.is_contiguous());
-
   TORCH_CHECK(xg.numel() < (1LL << 31),
               "x_gates too large for 32-bit staging offsets");
 }
@@ -388,18 +407,17 @@ std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
   gru_forward_checks(xg, w_hh, b_hh, h0, gamma, beta);
   int B = (int)xg.size(0), TT = (int)xg.size(1);
   int C = (int)h0.size(1), H = (int)h0.size(2);
-  auto dt = xg.scalar_type();
   auto h_all = at::empty({B, TT, C, H}, xg.options());
   auto saves = save ? at::empty({B, TT, C, 2 * H}, xg.options())
                     : at::empty({0}, xg.options());
-  // the GEMM streams a bf16 weight image from L2 regardless of T
-  auto w_gemm = w_hh.scalar_type() == at::kBFloat16
-                    ? w_hh
-                    : w_hh.to(at::kBFloat16);
-  dr_gru_fwd(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w_gemm.data_ptr(),
-             b_hh.data_ptr<float>(), h0.data_ptr(), h_all.data_ptr(),
-             save ? saves.data_ptr() : nullptr, B, TT, C, reverse ? 1 : 0,
-             save ? 1 : 0, fp8 ? 1 : 0, dt == at::kBFloat16, cur_stream());
+  auto w_gemm = gru_w_gemm(w_hh);
+  gru_launch_check(
+      dr_gru_fwd(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                 w_gemm.data_ptr(), b_hh.data_ptr<float>(), h0.data_ptr(),
+                 h_all.data_ptr(), save ? saves.data_ptr() : nullptr, B, TT, C,
+                 reverse ? 1 : 0, save ? 1 : 0, fp8 ? 1 : 0, is_bf16(xg),
+                 cur_stream()),
+      "gru forward");
   return {h_all, saves};
 }
 
@@ -420,9 +438,6 @@ std::vector<at::Tensor> gru_seq_decode(at::Tensor xg, at::Tensor w_hh,
   gru_forward_checks(xg, w_hh, b_hh, h0, gamma, beta);
   int B = (int)xg.size(0), TT = (int)xg.size(1);
   int C = (int)h0.size(1), H = (int)h0.size(2);
-  TORCH_CHECK(h0.size(0) == B && beta.sizes() == gamma.sizes() &&
-                  b_hh.numel() == 3 * H,
-              "gru decode: operand shapes do not match x_gates (B, T, 3H)");
   TORCH_CHECK(O >= 1 && O <= 32, "fused head decode needs 1 <= O <= 32, got ", O);
   TORCH_CHECK(wh_fwd.scalar_type() == at::kBFloat16 &&
                   wh_fwd.sizes() == at::IntArrayRef({32, H}) &&
@@ -431,20 +446,18 @@ std::vector<at::Tensor> gru_seq_decode(at::Tensor xg, at::Tensor w_hh,
   TORCH_CHECK((int64_t)B * TT * C * O < (1LL << 31),
               "decode output too large for 32-bit store offsets");
   const int* lens = lengths_ptr(lengths, xg, B, "gru decode lengths");
-  auto dt = xg.scalar_type();
   // with lengths the kernel stores valid positions only: padding stays zero
   auto out = lens ? at::zeros({B, TT, C, O}, xg.options())
                   : at::empty({B, TT, C, O}, xg.options());
   auto h_last = at::empty({B, C, H}, xg.options());
-  auto w_gemm = w_hh.scalar_type() == at::kBFloat16
-                    ? w_hh
-                    : w_hh.to(at::kBFloat16);
-  int err = dr_gru_decode(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                          w_gemm.data_ptr(), b_hh.data_ptr<float>(),
-                          h0.data_ptr(), wh_fwd.data_ptr(), out.data_ptr(),
-                          h_last.data_ptr(), B, TT, C, (int)O, reverse ? 1 : 0,
-                          fp8 ? 1 : 0, dt == at::kBFloat16, lens, cur_stream());
-  TORCH_CHECK(err == 0, "gru decode kernel launch failed (HIP error ", err, ")");
+  auto w_gemm = gru_w_gemm(w_hh);
+  gru_launch_check(
+      dr_gru_decode(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                    w_gemm.data_ptr(), b_hh.data_ptr<float>(), h0.data_ptr(),
+                    wh_fwd.data_ptr(), out.data_ptr(), h_last.data_ptr(), B, TT,
+                    C, (int)O, reverse ? 1 : 0, fp8 ? 1 : 0, is_bf16(xg), lens,
+                    cur_stream()),
+      "gru decode");
   return {out, h_last};
 }
 
@@ -503,12 +516,14 @@ static std::vector<at::Tensor> gru_backward_impl(
   TORCH_CHECK(grad_h.is_contiguous() && h_all.is_contiguous() && saves.is_contiguous());
   auto dpre = at::empty({B, TT, C, 4 * H}, grad_h.options());
   auto dh0 = at::empty({B, C, H}, grad_h.options().dtype(at::kFloat));
-  dr_gru_bwd(grad_h.data_ptr(), wh_img ? wh_img->data_ptr() : nullptr, O,
-             w_img.data_ptr(), w_fwd.data_ptr(), xg.data_ptr(),
-             gamma.data_ptr(), beta.data_ptr(), b_hh.data_ptr<float>(),
-             h0.data_ptr(), h_all.data_ptr(), saves.data_ptr(), dpre.data_ptr(),
-             dh0.data_ptr<float>(), B, TT, C, reverse ? 1 : 0,
-             dt == at::kBFloat16, cur_stream());
+  gru_launch_check(
+      dr_gru_bwd(grad_h.data_ptr(), wh_img ? wh_img->data_ptr() : nullptr, O,
+                 w_img.data_ptr(), w_fwd.data_ptr(), xg.data_ptr(),
+                 gamma.data_ptr(), beta.data_ptr(), b_hh.data_ptr<float>(),
+                 h0.data_ptr(), h_all.data_ptr(), saves.data_ptr(),
+                 dpre.data_ptr(), dh0.data_ptr<float>(), B, TT, C,
+                 reverse ? 1 : 0, dt == at::kBFloat16, cur_stream()),
+      "gru backward");
   return {dpre, dh0};
 }
 
@@ -546,11 +561,12 @@ std::vector<at::Tensor> gru_bwd_reduce(at::Tensor dpre, at::Tensor gamma,
   // pi-layout staging images (see pi_permute_rows_kernel)
   auto gamma_pi = at::empty_like(gamma);
   auto xg_pi = at::empty_like(xg);
-  dr_gru_bwd_reduce(dpre.data_ptr(), gamma.data_ptr(), xg.data_ptr(),
-                    dxg.data_ptr(), dgamma.data_ptr<float>(),
-                    dbeta.data_ptr<float>(), gamma_pi.data_ptr(),
-                    xg_pi.data_ptr(), BT, C,
-                    dpre.scalar_type() == at::kBFloat16, cur_stream());
+  gru_launch_check(
+      dr_gru_bwd_reduce(dpre.data_ptr(), gamma.data_ptr(), xg.data_ptr(),
+                        dxg.data_ptr(), dgamma.data_ptr<float>(),
+                        dbeta.data_ptr<float>(), gamma_pi.data_ptr(),
+                        xg_pi.data_ptr(), BT, C, is_bf16(dpre), cur_stream()),
+      "gru backward reductions");
   return {dxg, dgamma, dbeta};
 }
 

@@ -5,19 +5,9 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp8.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <algorithm>
 
 #define DR_WAVE 64  // CDNA wavefront width (gfx950)
-
-#define DR_HIP_CHECK(expr)                                                     \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      printf("HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__,       \
-             __LINE__);                                                        \
-    }                                                                          \
-  } while (0)
 
 namespace dr {
 

@@ -30,6 +30,8 @@
 // Fixed geometry: H = 128, 3H = 384, 64 rows/block, 4 waves, 256 threads.
 #include "common.h"
 
+#include <type_traits>
+
 namespace dr {
 
 constexpr int H = 128;        // hidden size (fixed)
@@ -42,19 +44,37 @@ constexpr int KT = H / 32;    // K-tiles of 32 in the fwd GEMM (4)
 constexpr int NT = G3H / 16;  // N-tiles of 16 (24)
 constexpr int XG_SLOTS = 32;  // distinct batch indices a 64-row tile may span
 
-// forward LDS offsets (single dynamic region, all 16B aligned).
+constexpr int LDS_MAX = 163840;  // dynamic LDS one workgroup may declare
+
+// Dynamic-LDS layout of gru_fwd_kernel<., ., FP8, NSUB, HEADS> (one region,
+// every offset 16 B aligned): the kernel takes its pointers from it and the
+// launcher its size.
 // Forward stages W in LDS (an L2-streamed W was measured SLOWER for the
 // forward: 96 KB/wave/step of L2 B-fragment traffic outweighed the
-// occupancy gain); the backward streams W from L2 instead (its register
-// budget allows 2 waves/SIMD there, and it has no LDS at all).
-constexpr int LDS_W = 0;                       // 384 x 128 bf16 swizzled (98304 B)
-constexpr int LDS_H = LDS_W + G3H * H * 2;     // 64 x 128 bf16 swizzled (16384 B)
-constexpr int LDS_XG = LDS_H + ROWS * H * 2;   // 32 x 384 bf16 (24576 B)
-constexpr int LDS_FWD_TOTAL = LDS_XG + XG_SLOTS * G3H * 2;  // 139264 B
+// occupancy gain).
+template <bool FP8, int NSUB, bool HEADS>
+struct FwdLds {
+  static constexpr int ELT = FP8 ? 1 : 2;                  // GEMM-tile element bytes
+  static constexpr int W = 0;                              // 384 x 128 swizzled
+  static constexpr int WH = W + G3H * H * ELT;             // (HEADS) 32 x 128 bf16 swizzled
+  static constexpr int HM = WH + (HEADS ? 32 * H * 2 : 0); // h mirror, ROWS*NSUB x 128 swizzled
+  static constexpr int XG = HM + ROWS * NSUB * H * ELT;    // 32 x 384 bf16, pi layout
+  static constexpr int TOTAL = XG + XG_SLOTS * G3H * 2;
+  static_assert(TOTAL <= LDS_MAX, "forward LDS layout exceeds a workgroup's LDS");
+};
 
-// backward uses NO LDS: the pi-permuted W image stays in L2 (96 KB, shared
-// by every block) so occupancy is VGPR-bound (2-3 waves/SIMD) instead of
-// LDS-bound (1 wave/SIMD) — the kernel is latency-bound, occupancy hides it.
+// Same for gru_bwd_kernel<., NSUB, FUSED>.  NSUB == 1 uses NO LDS: the
+// pi-permuted W image stays in L2 (96 KB, shared by every block) so occupancy
+// is VGPR-bound (2-3 waves/SIMD) instead of LDS-bound (1 wave/SIMD) — the
+// kernel is latency-bound, occupancy hides it.
+template <int NSUB, bool FUSED>
+struct BwdLds {
+  static constexpr int W = 0;                    // 128 x 384 bf16, swz768 rows
+  static constexpr int WN = W + H * G3H * 2;     // 128 x 128 bf16 swizzled
+  static constexpr int WH = WN + H * H * 2;      // (FUSED) 128 x 32 bf16 linear
+  static constexpr int TOTAL = NSUB == 2 ? WH + (FUSED ? H * 32 * 2 : 0) : 0;
+  static_assert(TOTAL <= LDS_MAX, "backward LDS layout exceeds a workgroup's LDS");
+};
 
 // swizzled byte address inside a row-major [rows][128] bf16 tile (256 B rows)
 __device__ __forceinline__ int swz(int row, int k_elem) {
@@ -208,13 +228,13 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
   static_assert(!(HEADS && SAVE), "the head phase is inference-only");
   static_assert(HEADS || !VARLEN, "per-row lengths exist in the decode kernel only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int ELT = FP8 ? 1 : 2;             // GEMM-tile element bytes
+  using L = FwdLds<FP8, NSUB, HEADS>;
   constexpr int BROWS = ROWS * NSUB;           // rows per block
   constexpr int BTHREADS = THREADS * NSUB;
-  char* Wl = smem;
-  char* WHl = smem + G3H * H * ELT;            // (HEADS) 32 x 128 bf16 swizzled
-  char* Hl = WHl + (HEADS ? 32 * H * 2 : 0);
-  char* XGl = Hl + BROWS * H * ELT;
+  char* Wl = smem + L::W;
+  char* WHl = smem + L::WH;
+  char* Hl = smem + L::HM;
+  char* XGl = smem + L::XG;
   // gamma/beta/b_hh in registers (NSUB == 1) or streamed per step
   constexpr bool GB_REGS = (NSUB == 1) && !(VARLEN && FP8);
 
@@ -661,8 +681,9 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
     float* __restrict__ dh0,        // (B, C, H)
     int B, int TT, int C, int reverse, int O) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* wn_lds = smem + H * G3H * 2;   // (NSUB==2) 128 x 128 bf16 swizzled
-  char* wh_lds = wn_lds + H * H * 2;   // (NSUB==2, FUSED) 128 x 32 bf16 linear
+  using L = BwdLds<NSUB, FUSED>;       // the pi W image sits at smem itself
+  char* wn_lds = smem + L::WN;         // (NSUB==2) W_hn rows
+  char* wh_lds = smem + L::WH;         // (NSUB==2, FUSED) head weight image
   const int tid = threadIdx.x;
   const int wv = tid / DR_WAVE;
   const int lane = tid % DR_WAVE;
@@ -1075,291 +1096,213 @@ __global__ void gru_dgamma_kernel(const T* __restrict__ dpre,   // (BT, C, 4H) p
 }
 
 // ------------------------------------------------------------- launchers
-// fp8 tiles halve the GEMM-side LDS: 48K W + 8K h + 24K xg
-constexpr int LDS_FWD_FP8 = G3H * H + ROWS * H + XG_SLOTS * G3H * 2;  // 81920 B
-// 8-wave variant: 96K W + 32K h(128 rows) + 24K xg
-constexpr int LDS_FWD_8W = G3H * H * 2 + 2 * ROWS * H * 2 + XG_SLOTS * G3H * 2;
+// Every launch function returns the hipError_t of its set-up or launch, and
+// the dr_gru_* entries hand it to the binding as an int (0 = success).
 
-template <typename T>
-static void gru_fwd_launch_t(const void* xg, const void* gamma, const void* beta,
-                             const void* w_gemm, const float* b_hh, const void* h0,
-                             void* h_all, void* saves, int B, int TT, int C,
-                             int reverse, int save, int fp8, hipStream_t stream) {
-  int64_t R = (int64_t)B * C;
-  int grid = (int)((R + ROWS - 1) / ROWS);
-  static bool attr_set = false;
-  if (!attr_set) {
-    DR_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&gru_fwd_kernel<T, true>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_TOTAL));
-    DR_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&gru_fwd_kernel<T, false>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_TOTAL));
-    DR_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&gru_fwd_kernel<T, false, true>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_FP8));
-    DR_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&gru_fwd_kernel<T, true, false, 2>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_8W));
-    DR_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&gru_fwd_kernel<T, false, false, 2>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_8W));
-    attr_set = true;
-  }
-  int tiles128 = (int)((R + 2 * ROWS - 1) / (2 * ROWS));
-  if (!fp8 && tiles128 >= 192 && C >= 5) {
-    // 8-wave 128-row variant: 2 waves/SIMD (needs enough tiles + xg slots)
-    if (save)
-      hipLaunchKernelGGL((gru_fwd_kernel<T, true, false, 2>), dim3(tiles128),
-                         dim3(2 * THREADS), LDS_FWD_8W, stream, (const T*)xg,
-                         (const T*)gamma, (const T*)beta, (const uint16_t*)w_gemm,
-                         b_hh, (const T*)h0, (T*)h_all, (T*)saves, B, TT, C,
-                         reverse, nullptr, nullptr, nullptr, 0, nullptr);
-    else
-      hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 2>), dim3(tiles128),
-                         dim3(2 * THREADS), LDS_FWD_8W, stream, (const T*)xg,
-                         (const T*)gamma, (const T*)beta, (const uint16_t*)w_gemm,
-                         b_hh, (const T*)h0, (T*)h_all, (T*)saves, B, TT, C,
-                         reverse, nullptr, nullptr, nullptr, 0, nullptr);
-    return;
-  }
-  if (fp8)
-    hipLaunchKernelGGL((gru_fwd_kernel<T, false, true>), dim3(grid), dim3(THREADS),
-                       LDS_FWD_FP8, stream, (const T*)xg, (const T*)gamma,
-                       (const T*)beta, (const uint16_t*)w_gemm, b_hh, (const T*)h0,
-                       (T*)h_all, (T*)saves, B, TT, C, reverse, nullptr, nullptr,
-                       nullptr, 0, nullptr);
-  else if (save)
-    hipLaunchKernelGGL((gru_fwd_kernel<T, true>), dim3(grid), dim3(THREADS),
-                       LDS_FWD_TOTAL, stream, (const T*)xg, (const T*)gamma,
-                       (const T*)beta, (const uint16_t*)w_gemm, b_hh, (const T*)h0,
-                       (T*)h_all, (T*)saves, B, TT, C, reverse, nullptr, nullptr,
-                       nullptr, 0, nullptr);
-  else
-    hipLaunchKernelGGL((gru_fwd_kernel<T, false>), dim3(grid), dim3(THREADS),
-                       LDS_FWD_TOTAL, stream, (const T*)xg, (const T*)gamma,
-                       (const T*)beta, (const uint16_t*)w_gemm, b_hh, (const T*)h0,
-                       (T*)h_all, (T*)saves, B, TT, C, reverse, nullptr, nullptr,
-                       nullptr, 0, nullptr);
+// run f with the IO element type as a tag: f(TypeTag<uint16_t>) or <float>
+template <typename T> struct TypeTag { using type = T; };
+template <typename F>
+static hipError_t with_io_type(int is_bf16, F&& f) {
+  return is_bf16 ? f(TypeTag<uint16_t>{}) : f(TypeTag<float>{});
 }
 
-// HEADS decode: same three variants behind the same dispatch conditions as
-// gru_fwd_launch_t.  The 8 KB head weight image joins every variant's LDS:
-// 147,456 B (4-wave), 90,112 B (FP8), 163,840 B (8-wave: all a workgroup may
-// declare).
-constexpr int LDS_WH = 32 * H * 2;  // 8192 B
-
-// VARLEN: the per-row-length twins (lens = (B,) int32 on the device), same
-// LDS sizes and the same dispatch conditions.
-template <typename T, bool VARLEN>
-static int gru_decode_launch_t(const void* xg, const void* gamma, const void* beta,
-                               const void* w_gemm, const float* b_hh,
-                               const void* h0, const void* wh_fwd, void* out,
-                               void* h_last, int B, int TT, int C, int O,
-                               int reverse, int fp8, const int* lens,
-                               hipStream_t stream) {
-  int64_t R = (int64_t)B * C;
-  int grid = (int)((R + ROWS - 1) / ROWS);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(
-            &gru_fwd_kernel<T, false, false, 1, true, VARLEN>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_TOTAL + LDS_WH);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(
-          reinterpret_cast<const void*>(
-              &gru_fwd_kernel<T, false, true, 1, true, VARLEN>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_FP8 + LDS_WH);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(
-          reinterpret_cast<const void*>(
-              &gru_fwd_kernel<T, false, false, 2, true, VARLEN>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD_8W + LDS_WH);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  int tiles128 = (int)((R + 2 * ROWS - 1) / (2 * ROWS));
-  if (!fp8 && tiles128 >= 192 && C >= 5)
-    hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 2, true, VARLEN>),
-                       dim3(tiles128), dim3(2 * THREADS), LDS_FWD_8W + LDS_WH,
-                       stream, (const T*)xg, (const T*)gamma, (const T*)beta,
-                       (const uint16_t*)w_gemm, b_hh, (const T*)h0, nullptr,
-                       nullptr, B, TT, C, reverse, (const uint16_t*)wh_fwd,
-                       (T*)out, (T*)h_last, O, lens);
-  else if (fp8)
-    hipLaunchKernelGGL((gru_fwd_kernel<T, false, true, 1, true, VARLEN>),
-                       dim3(grid), dim3(THREADS), LDS_FWD_FP8 + LDS_WH, stream,
-                       (const T*)xg, (const T*)gamma, (const T*)beta,
-                       (const uint16_t*)w_gemm, b_hh, (const T*)h0, nullptr,
-                       nullptr, B, TT, C, reverse, (const uint16_t*)wh_fwd,
-                       (T*)out, (T*)h_last, O, lens);
-  else
-    hipLaunchKernelGGL((gru_fwd_kernel<T, false, false, 1, true, VARLEN>),
-                       dim3(grid), dim3(THREADS), LDS_FWD_TOTAL + LDS_WH, stream,
-                       (const T*)xg, (const T*)gamma, (const T*)beta,
-                       (const uint16_t*)w_gemm, b_hh, (const T*)h0, nullptr,
-                       nullptr, B, TT, C, reverse, (const uint16_t*)wh_fwd,
-                       (T*)out, (T*)h_last, O, lens);
-  return (int)hipGetLastError();   // a rejected launch is the caller's error
+// The forward kernel's tile variant, chosen once for the sequence and the
+// decode entry: f(FwdTile<FP8, NSUB>).
+template <bool FP8_, int NSUB_> struct FwdTile {
+  static constexpr bool FP8 = FP8_;
+  static constexpr int NSUB = NSUB_;
+};
+template <typename F>
+static hipError_t with_fwd_tile(int B, int C, int fp8, F&& f) {
+  const int64_t tiles128 = ((int64_t)B * C + 2 * ROWS - 1) / (2 * ROWS);
+  // 8-wave 128-row variant: 2 waves/SIMD.  It needs enough tiles to fill the
+  // chip at one block per CU, and C >= 5: its 128 rows must not span more
+  // than XG_SLOTS batch indices (C = 4 spans up to 33).
+  const bool wide = !fp8 && tiles128 >= 192 && C >= 5;
+  if (!wide && !fp8) return f(FwdTile<false, 1>{});
+  if (fp8) return f(FwdTile<true, 1>{});
+  return f(FwdTile<false, 2>{});
 }
 
-template <typename T, bool FUSED>
-static void gru_bwd_launch_t(const void* grad_h, const void* wh_img,
-                             const void* w_img, const void* w_fwd, const void* xg,
-                             const void* gamma, const void* beta,
-                             const float* b_hh, const void* h0,
-                             const void* h_all, const void* saves, void* dpre,
-                             float* dh0, int B, int TT, int C, int reverse, int O,
-                             hipStream_t stream) {
-  int64_t R = (int64_t)B * C;
-  int tiles128 = (int)((R + 2 * ROWS - 1) / (2 * ROWS));
-  if (tiles128 >= 192) {
-    // enough 128-row tiles to fill the chip at 1 block/CU: LDS-W variant
-    // 96 KB W image + 32 KB W_hn (+ 8 KB head weight image when FUSED)
-    constexpr int LDS_WB = H * G3H * 2 + H * H * 2 + (FUSED ? H * 32 * 2 : 0);
-    static bool attr_set = false;
-    if (!attr_set) {
-      DR_HIP_CHECK(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&gru_bwd_kernel<T, 2, FUSED>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WB));
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((gru_bwd_kernel<T, 2, FUSED>), dim3(tiles128),
-                       dim3(2 * THREADS), LDS_WB, stream, (const T*)grad_h,
-                       (const uint16_t*)wh_img, (const uint16_t*)w_img,
-                       (const uint16_t*)w_fwd, (const T*)xg, (const T*)gamma,
-                       (const T*)beta, b_hh, (const T*)h0, (const T*)h_all,
-                       (const T*)saves, (T*)dpre, dh0, B, TT, C, reverse, O);
-    return;
-  }
-  int grid = (int)((R + ROWS - 1) / ROWS);
-  hipLaunchKernelGGL((gru_bwd_kernel<T, 1, FUSED>), dim3(grid), dim3(THREADS), 0,
-                     stream, (const T*)grad_h, (const uint16_t*)wh_img,
-                     (const uint16_t*)w_img, (const uint16_t*)w_fwd,
-                     (const T*)xg, (const T*)gamma, (const T*)beta, b_hh,
-                     (const T*)h0, (const T*)h_all, (const T*)saves, (T*)dpre,
-                     dh0, B, TT, C, reverse, O);
+// Raises a kernel's dynamic-LDS limit.  Each launch function keeps the result
+// in a function-local static: set once per instantiation (thread-safe, and
+// only for the variant that runs), a failure is returned by every later call.
+// Once per process, not per device: a second device used by the same process
+// would launch without the attribute.
+template <typename K>
+static hipError_t allow_lds(K kernel, int bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
+struct FwdArgs {
+  const void *xg, *gamma, *beta, *w_gemm;
+  const float* b_hh;
+  const void* h0;
+  void *h_all, *saves;     // sequence entry (saves: SAVE only); decode: null
+  int B, TT, C, reverse;
+  const void* wh_fwd;      // decode entry; sequence: null / 0
+  void *out, *h_last;
+  int O;
+  const int* lens;         // VARLEN only
+  hipStream_t stream;
+};
+
+template <typename T, bool SAVE, bool FP8, int NSUB, bool HEADS, bool VARLEN>
+static hipError_t gru_fwd_launch(const FwdArgs& a) {
+  constexpr int LDS = FwdLds<FP8, NSUB, HEADS>::TOTAL;
+  static const hipError_t attr =
+      allow_lds(&gru_fwd_kernel<T, SAVE, FP8, NSUB, HEADS, VARLEN>, LDS);
+  if (attr != hipSuccess) return attr;
+  const int64_t R = (int64_t)a.B * a.C;
+  const int grid = (int)((R + ROWS * NSUB - 1) / (ROWS * NSUB));
+  hipLaunchKernelGGL((gru_fwd_kernel<T, SAVE, FP8, NSUB, HEADS, VARLEN>),
+                     dim3(grid), dim3(THREADS * NSUB), LDS, a.stream,
+                     (const T*)a.xg, (const T*)a.gamma, (const T*)a.beta,
+                     (const uint16_t*)a.w_gemm, a.b_hh, (const T*)a.h0,
+                     (T*)a.h_all, (T*)a.saves, a.B, a.TT, a.C, a.reverse,
+                     (const uint16_t*)a.wh_fwd, (T*)a.out, (T*)a.h_last, a.O,
+                     a.lens);
+  return hipGetLastError();
+}
+
+struct BwdArgs {
+  const void *grad, *wh_img, *w_img, *w_fwd, *xg, *gamma, *beta;
+  const float* b_hh;
+  const void *h0, *h_all, *saves;
+  void* dpre;
+  float* dh0;
+  int B, TT, C, reverse, O;
+  hipStream_t stream;
+};
+
+template <typename T, int NSUB, bool FUSED>
+static hipError_t gru_bwd_launch(const BwdArgs& a) {
+  constexpr int LDS = BwdLds<NSUB, FUSED>::TOTAL;
+  static const hipError_t attr =
+      LDS ? allow_lds(&gru_bwd_kernel<T, NSUB, FUSED>, LDS) : hipSuccess;
+  if (attr != hipSuccess) return attr;
+  const int64_t R = (int64_t)a.B * a.C;
+  const int grid = (int)((R + ROWS * NSUB - 1) / (ROWS * NSUB));
+  hipLaunchKernelGGL((gru_bwd_kernel<T, NSUB, FUSED>), dim3(grid),
+                     dim3(THREADS * NSUB), LDS, a.stream, (const T*)a.grad,
+                     (const uint16_t*)a.wh_img, (const uint16_t*)a.w_img,
+                     (const uint16_t*)a.w_fwd, (const T*)a.xg,
+                     (const T*)a.gamma, (const T*)a.beta, a.b_hh,
+                     (const T*)a.h0, (const T*)a.h_all, (const T*)a.saves,
+                     (T*)a.dpre, a.dh0, a.B, a.TT, a.C, a.reverse, a.O);
+  return hipGetLastError();
 }
 
 template <typename T>
-static void gru_reduce_launch_t(const void* dpre, const void* gamma, const void* xg,
-                                void* dxg, float* dgamma, float* dbeta,
-                                void* gamma_pi, void* xg_pi, int64_t BT,
-                                int C, hipStream_t stream) {
+static hipError_t gru_reduce_launch(const void* dpre, const void* gamma,
+                                    const void* xg, void* dxg, float* dgamma,
+                                    float* dbeta, void* gamma_pi, void* xg_pi,
+                                    int64_t BT, int C, hipStream_t stream) {
+  auto chunk_grid = [](int64_t rows) {
+    return (int)std::min<int64_t>((rows * 48 + 255) / 256, 4096);
+  };
   // stage pi-layout images of gamma and xg (once per backward, ~47 MB at
   // bench scale) so the reduction inner loops are pure 16-byte loads
-  {
-    int64_t n = (int64_t)C * 48;
-    int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL((pi_permute_rows_kernel<T>), dim3(grid), dim3(256), 0,
-                       stream, (const T*)gamma, (T*)gamma_pi, (int64_t)C);
-  }
-  {
-    int64_t n = BT * 48;
-    int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL((pi_permute_rows_kernel<T>), dim3(grid), dim3(256), 0,
-                       stream, (const T*)xg, (T*)xg_pi, BT);
-  }
-  {
-    int64_t n = BT * 48;
-    int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL((gru_dxg_kernel<T>), dim3(grid), dim3(256), 0, stream,
-                       (const T*)dpre, (const T*)gamma_pi, (T*)dxg, BT, C);
-  }
-  {
-    int n_threads = C * 64;
-    int gx = (n_threads + 255) / 256;
-    int gy = 128;  // BT slices (parallelism for small C; atomics stay cheap)
-    hipLaunchKernelGGL((gru_dgamma_kernel<T>), dim3(gx, gy), dim3(256), 0, stream,
-                       (const T*)dpre, (const T*)xg_pi, dgamma, dbeta, BT, C);
-  }
+  hipLaunchKernelGGL((pi_permute_rows_kernel<T>), dim3(chunk_grid(C)), dim3(256),
+                     0, stream, (const T*)gamma, (T*)gamma_pi, (int64_t)C);
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL((pi_permute_rows_kernel<T>), dim3(chunk_grid(BT)), dim3(256),
+                     0, stream, (const T*)xg, (T*)xg_pi, BT);
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL((gru_dxg_kernel<T>), dim3(chunk_grid(BT)), dim3(256), 0,
+                     stream, (const T*)dpre, (const T*)gamma_pi, (T*)dxg, BT, C);
+  if (hipError_t e = hipGetLastError()) return e;
+  const int gx = (C * 64 + 255) / 256;
+  const int gy = 128;  // BT slices (parallelism for small C; atomics stay cheap)
+  hipLaunchKernelGGL((gru_dgamma_kernel<T>), dim3(gx, gy), dim3(256), 0, stream,
+                     (const T*)dpre, (const T*)xg_pi, dgamma, dbeta, BT, C);
+  return hipGetLastError();
 }
 
 }  // namespace dr
 
 extern "C" {
 
-void dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
-                const void* w_hh, const float* b_hh, const void* h0, void* h_all,
-                void* saves, int B, int TT, int C, int reverse, int save,
-                int fp8, int is_bf16, hipStream_t stream) {
-  if (is_bf16)
-    dr::gru_fwd_launch_t<uint16_t>(xg, gamma, beta, w_hh, b_hh, h0, h_all, saves,
-                                   B, TT, C, reverse, save, fp8, stream);
-  else
-    dr::gru_fwd_launch_t<float>(xg, gamma, beta, w_hh, b_hh, h0, h_all, saves,
-                                B, TT, C, reverse, save, fp8, stream);
+int dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
+               const void* w_hh, const float* b_hh, const void* h0, void* h_all,
+               void* saves, int B, int TT, int C, int reverse, int save,
+               int fp8, int is_bf16, hipStream_t stream) {
+  const dr::FwdArgs a{xg, gamma, beta, w_hh, b_hh, h0, h_all, saves, B, TT, C,
+                      reverse, nullptr, nullptr, nullptr, 0, nullptr, stream};
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    using T = typename decltype(io)::type;
+    return dr::with_fwd_tile(B, C, fp8, [&](auto tile) {
+      using V = decltype(tile);
+      // the fp8 tiles are inference-only: no SAVE instantiation exists
+      if constexpr (!V::FP8)
+        if (save) return dr::gru_fwd_launch<T, true, false, V::NSUB, false, false>(a);
+      return dr::gru_fwd_launch<T, false, V::FP8, V::NSUB, false, false>(a);
+    });
+  });
 }
 
 // Inference decode: GRU sequence + head projection, no h_all.  wh_fwd is the
 // (32, H) bf16 head weight image, rows >= O exact zero.  lens == nullptr:
 // every row runs all TT steps; otherwise (B,) int32 per-sample lengths on the
-// device and out must arrive zeroed.  Returns the HIP error of the attribute
-// setup or the launch (0 = success).
+// device and out must arrive zeroed.
 int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
                   const void* w_hh, const float* b_hh, const void* h0,
                   const void* wh_fwd, void* out, void* h_last, int B, int TT,
                   int C, int O, int reverse, int fp8, int is_bf16,
                   const int* lens, hipStream_t stream) {
-  if (lens != nullptr) {
-    if (is_bf16)
-      return dr::gru_decode_launch_t<uint16_t, true>(
-          xg, gamma, beta, w_hh, b_hh, h0, wh_fwd, out, h_last, B, TT, C, O,
-          reverse, fp8, lens, stream);
-    return dr::gru_decode_launch_t<float, true>(xg, gamma, beta, w_hh, b_hh, h0,
-                                                wh_fwd, out, h_last, B, TT, C, O,
-                                                reverse, fp8, lens, stream);
-  }
-  if (is_bf16)
-    return dr::gru_decode_launch_t<uint16_t, false>(
-        xg, gamma, beta, w_hh, b_hh, h0, wh_fwd, out, h_last, B, TT, C, O,
-        reverse, fp8, nullptr, stream);
-  return dr::gru_decode_launch_t<float, false>(xg, gamma, beta, w_hh, b_hh, h0,
-                                               wh_fwd, out, h_last, B, TT, C, O,
-                                               reverse, fp8, nullptr, stream);
+  const dr::FwdArgs a{xg, gamma, beta, w_hh, b_hh, h0, nullptr, nullptr, B, TT, C,
+                      reverse, wh_fwd, out, h_last, O, lens, stream};
+  auto run = [&](auto varlen) {
+    return dr::with_io_type(is_bf16, [&](auto io) {
+      using T = typename decltype(io)::type;
+      return dr::with_fwd_tile(B, C, fp8, [&](auto tile) {
+        using V = decltype(tile);
+        return dr::gru_fwd_launch<T, false, V::FP8, V::NSUB, true,
+                                  decltype(varlen)::value>(a);
+      });
+    });
+  };
+  return (int)(lens != nullptr ? run(std::true_type{}) : run(std::false_type{}));
 }
 
 // wh_img == nullptr: grad is grad_h (B, TT, C, H), the unfused path.
 // Otherwise grad is the heads' grad_part (B, TT, C, O) and wh_img the (H, 32)
 // bf16 zero-padded transposed head weight image.
-void dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
-                const void* w_fwd, const void* xg, const void* gamma,
-                const void* beta, const float* b_hh, const void* h0,
-                const void* h_all, const void* saves, void* dpre, float* dh0,
-                int B, int TT, int C, int reverse, int is_bf16,
-                hipStream_t stream) {
-  if (wh_img != nullptr) {
-    if (is_bf16)
-      dr::gru_bwd_launch_t<uint16_t, true>(grad, wh_img, w_img, w_fwd, xg, gamma,
-                                           beta, b_hh, h0, h_all, saves, dpre,
-                                           dh0, B, TT, C, reverse, O, stream);
-    else
-      dr::gru_bwd_launch_t<float, true>(grad, wh_img, w_img, w_fwd, xg, gamma,
-                                        beta, b_hh, h0, h_all, saves, dpre, dh0,
-                                        B, TT, C, reverse, O, stream);
-    return;
-  }
-  if (is_bf16)
-    dr::gru_bwd_launch_t<uint16_t, false>(grad, nullptr, w_img, w_fwd, xg, gamma,
-                                          beta, b_hh, h0, h_all, saves, dpre,
-                                          dh0, B, TT, C, reverse, 0, stream);
-  else
-    dr::gru_bwd_launch_t<float, false>(grad, nullptr, w_img, w_fwd, xg, gamma,
-                                       beta, b_hh, h0, h_all, saves, dpre, dh0,
-                                       B, TT, C, reverse, 0, stream);
+int dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
+               const void* w_fwd, const void* xg, const void* gamma,
+               const void* beta, const float* b_hh, const void* h0,
+               const void* h_all, const void* saves, void* dpre, float* dh0,
+               int B, int TT, int C, int reverse, int is_bf16,
+               hipStream_t stream) {
+  const bool fused = wh_img != nullptr;
+  const dr::BwdArgs a{grad, wh_img, w_img, w_fwd, xg, gamma, beta, b_hh, h0,
+                      h_all, saves, dpre, dh0, B, TT, C, reverse, fused ? O : 0,
+                      stream};
+  // enough 128-row tiles to fill the chip at 1 block/CU: the LDS-W variant
+  const int64_t tiles128 = ((int64_t)B * C + 2 * dr::ROWS - 1) / (2 * dr::ROWS);
+  const bool lds_w = tiles128 >= 192;
+  auto run = [&](auto fused_tag) {
+    return dr::with_io_type(is_bf16, [&](auto io) {
+      using T = typename decltype(io)::type;
+      constexpr bool FUSED = decltype(fused_tag)::value;
+      return lds_w ? dr::gru_bwd_launch<T, 2, FUSED>(a)
+                   : dr::gru_bwd_launch<T, 1, FUSED>(a);
+    });
+  };
+  return (int)(fused ? run(std::true_type{}) : run(std::false_type{}));
 }
 
-void dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
-                       void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
-                       void* xg_pi, int64_t BT, int C, int is_bf16,
-                       hipStream_t stream) {
-  if (is_bf16)
-    dr::gru_reduce_launch_t<uint16_t>(dpre, gamma, xg, dxg, dgamma, dbeta,
-                                      gamma_pi, xg_pi, BT, C, stream);
-  else
-    dr::gru_reduce_launch_t<float>(dpre, gamma, xg, dxg, dgamma, dbeta,
-                                   gamma_pi, xg_pi, BT, C, stream);
+// returns the first failing launch's error
+int dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
+                      void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
+                      void* xg_pi, int64_t BT, int C, int is_bf16,
+                      hipStream_t stream) {
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    using T = typename decltype(io)::type;
+    return dr::gru_reduce_launch<T>(dpre, gamma, xg, dxg, dgamma, dbeta,
+                                    gamma_pi, xg_pi, BT, C, stream);
+  });
 }
 
 }  // extern "C"

@@ -191,14 +191,6 @@ class _LayerNormOp(nn.Module):
         return layer_norm(x, self.weight, self.bias, self.eps)
 
 
-def _mha(q, k, v, kv_lengths):
-    """mha_forward; the lengths argument is passed only when there is one, so
-    the fixed-length call is the one it always was."""
-    if kv_lengths is None:
-        return mha_forward(q, k, v)
-    return mha_forward(q, k, v, kv_lengths=kv_lengths)
-
-
 class _EncoderLayer(nn.Module):
     def __init__(self, cfg: DeepRestNetConfig) -> None:
         super().__init__()
@@ -219,7 +211,7 @@ class _EncoderLayer(nn.Module):
         h = self.ln1(x)
         qkv = self.qkv(h).view(B, T, 3, self.n_heads, D // self.n_heads)
         q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # (B,h,T,dh)
-        attn = _mha(q, k, v, kv_lengths)
+        attn = mha_forward(q, k, v, kv_lengths=kv_lengths)
         attn = attn.transpose(1, 2).reshape(B, T, D)
         x = x + self.dropout(self.proj(attn))
         h = self.ln2(x)
@@ -237,7 +229,7 @@ class _EncoderLayer(nn.Module):
         p, training = self.dropout.p, self.training
         qkv = self.qkv(h).view(B, T, 3, self.n_heads, D // self.n_heads)
         q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # (B,h,T,dh)
-        attn = _mha(q, k, v, kv_lengths)
+        attn = mha_forward(q, k, v, kv_lengths=kv_lengths)
         attn = attn.transpose(1, 2).reshape(B, T, D)
         x, h = dropout_add_layer_norm(self.proj(attn), x, self.ln2.weight,
                                       self.ln2.bias, p, training, self.ln2.eps)
@@ -312,27 +304,43 @@ class _GRUDecoderBank(nn.Module):
                     b.weight.mul_(0.1)
                     b.bias.zero_()
 
+    @property
+    def dirs(self) -> int:
+        return 2 if self.bidirectional else 1
+
+    def _of(self, name: str, d: int):
+        """Direction d's parameter or sub-module: the reverse direction's
+        carry the suffix "_r"."""
+        return getattr(self, name + ("_r" if d else ""))
+
+    def x_gates(self, enc: torch.Tensor, d: int) -> torch.Tensor:
+        return self._of("x_proj", d)(enc)                      # (B, T, 3H)
+
+    def film(self, comp: torch.Tensor, d: int):
+        """Direction d's FiLM condition (gamma, beta), each (C, 3H)."""
+        return self._of("cond_gamma", d)(comp), self._of("cond_beta", d)(comp)
+
+    def h0(self, comp: torch.Tensor, B: int, d: int) -> torch.Tensor:
+        """Direction d's initial state (B, C, H), contiguous."""
+        h0 = torch.tanh(self._of("h0_proj", d)(comp))
+        return h0.unsqueeze(0).expand(B, comp.shape[0], self.hidden).contiguous()
+
+    def operands(self, enc: torch.Tensor, comp: torch.Tensor, d: int):
+        """Direction d's ``(x_gates, w_hh, b_hh, h0, gamma, beta)``, the
+        leading arguments of the fused GRU ops."""
+        xg = self.x_gates(enc, d)
+        gamma, beta = self.film(comp, d)
+        return (xg, self._of("w_hh", d), self._of("b_hh", d),
+                self.h0(comp, enc.shape[0], d), gamma, beta)
+
     def forward(self, enc: torch.Tensor, comp: torch.Tensor, fp8: bool = False):
         """enc: (B, T, D); comp: (C, comp_dim) -> tuple of direction outputs
         (each (B, T, C, H)); the heads consume the halves separately so no
         concat copy is ever materialized."""
-        B = enc.shape[0]
-        C = comp.shape[0]
-        xg = self.x_proj(enc)                                  # (B, T, 3H)
-        gamma = self.cond_gamma(comp)                          # (C, 3H)
-        beta = self.cond_beta(comp)
-        h0 = torch.tanh(self.h0_proj(comp)).unsqueeze(0).expand(B, C, self.hidden)
-        out = fused_gru_sequence(xg, self.w_hh, self.b_hh, h0.contiguous(),
-                                 gamma, beta, reverse=False, fp8=fp8)
-        if not self.bidirectional:
-            return (out,)
-        xg_r = self.x_proj_r(enc)
-        gamma_r = self.cond_gamma_r(comp)
-        beta_r = self.cond_beta_r(comp)
-        h0_r = torch.tanh(self.h0_proj_r(comp)).unsqueeze(0).expand(B, C, self.hidden)
-        out_r = fused_gru_sequence(xg_r, self.w_hh_r, self.b_hh_r, h0_r.contiguous(),
-                                   gamma_r, beta_r, reverse=True, fp8=fp8)
-        return (out, out_r)
+        return tuple(
+            fused_gru_sequence(*self.operands(enc, comp, d), reverse=bool(d),
+                               fp8=fp8)
+            for d in range(self.dirs))
 
     def forward_heads(self, enc: torch.Tensor, comp: torch.Tensor,
                       w_heads: Sequence[torch.Tensor]) -> torch.Tensor:
@@ -340,19 +348,10 @@ class _GRUDecoderBank(nn.Module):
         (ops.fused_gru_heads): ``w_heads[d]`` is direction d's (O, H) head
         weight slice; returns the summed head output (B, T, C, O).  Same
         math as ``forward`` followed by a per-direction linear."""
-        B = enc.shape[0]
-        C = comp.shape[0]
         out = None
-        for d in range(2 if self.bidirectional else 1):
-            sfx = "_r" if d else ""
-            xg = getattr(self, "x_proj" + sfx)(enc)            # (B, T, 3H)
-            gamma = getattr(self, "cond_gamma" + sfx)(comp)    # (C, 3H)
-            beta = getattr(self, "cond_beta" + sfx)(comp)
-            h0 = torch.tanh(getattr(self, "h0_proj" + sfx)(comp))
-            h0 = h0.unsqueeze(0).expand(B, C, self.hidden).contiguous()
-            part = fused_gru_heads(xg, getattr(self, "w_hh" + sfx),
-                                   getattr(self, "b_hh" + sfx), h0, gamma, beta,
-                                   w_heads[d], reverse=bool(d))
+        for d in range(self.dirs):
+            part = fused_gru_heads(*self.operands(enc, comp, d), w_heads[d],
+                                   reverse=bool(d))
             out = part if out is None else out + part
         return out
 
@@ -363,22 +362,8 @@ class _GRUDecoderBank(nn.Module):
         returns ``(part (B, T, C, O), h_last (B, C, H))`` with ``part`` that
         direction's head output; the hidden sequence is never materialized.
         ``lengths`` (B,) int32: per-sample window lengths, see the op."""
-        B = enc.shape[0]
-        C = comp.shape[0]
-        sfx = "_r" if d else ""
-        xg = getattr(self, "x_proj" + sfx)(enc)                # (B, T, 3H)
-        gamma = getattr(self, "cond_gamma" + sfx)(comp)        # (C, 3H)
-        beta = getattr(self, "cond_beta" + sfx)(comp)
-        h0 = torch.tanh(getattr(self, "h0_proj" + sfx)(comp))
-        h0 = h0.unsqueeze(0).expand(B, C, self.hidden).contiguous()
-        if lengths is None:
-            return fused_gru_decode(xg, getattr(self, "w_hh" + sfx),
-                                    getattr(self, "b_hh" + sfx), h0, gamma, beta,
-                                    w_heads[d], reverse=bool(d), fp8=fp8)
-        return fused_gru_decode(xg, getattr(self, "w_hh" + sfx),
-                                getattr(self, "b_hh" + sfx), h0, gamma, beta,
-                                w_heads[d], reverse=bool(d), fp8=fp8,
-                                lengths=lengths)
+        return fused_gru_decode(*self.operands(enc, comp, d), w_heads[d],
+                                reverse=bool(d), fp8=fp8, lengths=lengths)
 
 
 # -------------------------------------------------------------------- model
@@ -447,109 +432,101 @@ class DeepRestNet(nn.Module):
         model returns for that window alone, nothing stored in the padding
         can reach it, and ``out[b, L:]`` is exact zero.  The lengths are
         read on the device only, so a captured graph stays valid when the
-        buffer is rewritten between replays."""
-        if lengths is not None:
-            return self._forward_lengths(traffic, lengths)
+        buffer is rewritten between replays.  With lengths every stage but
+        two is per-position; attention masks the padded keys and the decoders
+        run each sample's own steps (both inside their kernels on GPU)."""
         B, T, P = traffic.shape
-        x = self.in_proj(traffic)
-        x = x + self._pos_encoding(T, x.device, x.dtype)
-        x = self.in_norm(x)
-        if self.cfg.fused_residual_norm:
-            x = self._encode_fused(x)
-        else:
-            for layer in self.layers:
-                x = layer(x)
+        if lengths is not None:
+            if self.training or torch.is_grad_enabled():
+                raise ValueError(
+                    "lengths are inference-only: call model.eval() and run "
+                    "under torch.no_grad()")
+            if lengths.dim() != 1 or lengths.shape[0] != B:
+                raise ValueError(
+                    f"lengths must be ({B},), got {tuple(lengths.shape)}")
+            lengths = lengths.to(device=traffic.device, dtype=torch.int32)
+        x = self._encode(traffic, lengths)
         comp = self.graph()                                   # (C, comp_dim)
         fp8 = (self.cfg.fp8_inference and not self.training
                and traffic.is_cuda and not torch.is_grad_enabled())
-        if self._use_head_decode(x, comp):
-            w_dirs = self._head_weights_per_dir()
-            out = None
-            for d in range(len(w_dirs)):
-                part, _ = self.decoder.decode_heads(x, comp, w_dirs, fp8, d)
-                out = part if out is None else out + part
-            return self._finish_heads(out)
+        # with lengths always the decode op, whatever cfg.fused_head_decode
+        # says: it is the GRU entry that knows about lengths (native kernel
+        # on GPU when the shape fits it, the composed reference otherwise)
+        if lengths is not None or self._use_head_decode(x, comp):
+            preds = self._finish_heads(self._decode_sum(x, comp, fp8, lengths))
+            if lengths is None:
+                return preds
+            # metric_bias made the padded positions non-zero: zero them by
+            # select
+            valid = (torch.arange(T, device=preds.device)[None, :]
+                     < lengths.clamp(1, T)[:, None])
+            return torch.where(valid[:, :, None, None], preds,
+                               torch.zeros((), dtype=preds.dtype,
+                                           device=preds.device))
         if self._use_fused_heads(x, comp, fp8):
-            H = self.cfg.hidden
-            w_all = self._head_weights()
-            dirs = 2 if self.cfg.bidirectional else 1
-            w_dirs = [w_all[:, d * H : (d + 1) * H].contiguous()
-                      for d in range(dirs)]
-            return self._finish_heads(self.decoder.forward_heads(x, comp, w_dirs))
+            return self._finish_heads(self.decoder.forward_heads(
+                x, comp, self._head_weights_per_dir()))
         h_dirs = self.decoder(x, comp, fp8=fp8)               # tuple of (B,T,C,H)
         return self._apply_heads(h_dirs)
 
-    def _forward_lengths(self, traffic: torch.Tensor,
-                         lengths: torch.Tensor) -> torch.Tensor:
-        """forward() for windows of per-sample length.  Every stage but two
-        is per-position; attention masks the padded keys and the decoders
-        run each sample's own steps (both inside their kernels on GPU)."""
-        if self.training or torch.is_grad_enabled():
-            raise ValueError(
-                "lengths are inference-only: call model.eval() and run under "
-                "torch.no_grad()")
-        B, T, P = traffic.shape
-        if lengths.dim() != 1 or lengths.shape[0] != B:
-            raise ValueError(
-                f"lengths must be ({B},), got {tuple(lengths.shape)}")
-        lengths = lengths.to(device=traffic.device, dtype=torch.int32)
+    def _encode(self, traffic: torch.Tensor,
+                lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """traffic (B, T, P) -> encoder output (B, T, D); ``lengths`` as in
+        forward()."""
         x = self.in_proj(traffic)
-        x = x + self._pos_encoding(T, x.device, x.dtype)
+        x = x + self._pos_encoding(x.shape[1], x.device, x.dtype)
         x = self.in_norm(x)
         if self.cfg.fused_residual_norm:
-            x = self._encode_fused(x, lengths)
-        else:
-            for layer in self.layers:
-                x = layer(x, lengths)
-        comp = self.graph()                                   # (C, comp_dim)
-        fp8 = bool(self.cfg.fp8_inference and traffic.is_cuda)
-        # always the decode op, whatever cfg.fused_head_decode says: it is
-        # the GRU entry that knows about lengths (native kernel on GPU when
-        # the shape fits it, the composed reference otherwise)
+            return self._encode_fused(x, lengths)
+        for layer in self.layers:
+            x = layer(x, lengths)
+        return x
+
+    def _decode_sum(self, enc: torch.Tensor, comp: torch.Tensor, fp8: bool,
+                    lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Sum over directions of the decode op's head outputs (B, T, C, R*Q)."""
         w_dirs = self._head_weights_per_dir()
         out = None
         for d in range(len(w_dirs)):
-            part, _ = self.decoder.decode_heads(x, comp, w_dirs, fp8, d,
-                                                lengths=lengths)
+            part, _ = self.decoder.decode_heads(enc, comp, w_dirs, fp8, d, lengths)
             out = part if out is None else out + part
-        preds = self._finish_heads(out)
-        # metric_bias made the padded positions non-zero: zero them by select
-        valid = (torch.arange(T, device=preds.device)[None, :]
-                 < lengths.clamp(1, T)[:, None])
-        return torch.where(valid[:, :, None, None], preds,
-                           torch.zeros((), dtype=preds.dtype,
-                                       device=preds.device))
+        return out
+
+    def _native_heads_fit(self, enc: torch.Tensor, comp: torch.Tensor) -> bool:
+        """GPU input, the decoder runs the native GRU kernel, and all heads
+        together fit its head phase: one K=32 MFMA step in the backward, two
+        16-wide output tiles in the decode."""
+        return (enc.is_cuda
+                and gru_kernel_supports(self.cfg.hidden, comp.shape[0])
+                and len(self.heads) * len(self.cfg.quantiles) <= HEAD_FUSE_MAX_OUT)
 
     def _use_fused_heads(self, enc: torch.Tensor, comp: torch.Tensor,
                          fp8: bool) -> bool:
-        """cfg.fused_head_grad applies when the decoder runs the native GRU
-        kernel (not its fp8 inference variant), the head dropout is the
-        identity, and all heads together fit one K=32 MFMA step."""
-        if not self.cfg.fused_head_grad or fp8 or not enc.is_cuda:
-            return False
-        if not gru_kernel_supports(self.cfg.hidden, comp.shape[0]):
+        """cfg.fused_head_grad applies when the native kernel does (not its
+        fp8 inference variant) and the head dropout is the identity."""
+        if not self.cfg.fused_head_grad or fp8:
             return False
         if self.training and self.dropout.p > 0:
             return False
-        return len(self.heads) * len(self.cfg.quantiles) <= HEAD_FUSE_MAX_OUT
+        return self._native_heads_fit(enc, comp)
 
     def _use_head_decode(self, enc: torch.Tensor, comp: torch.Tensor) -> bool:
         """cfg.fused_head_decode applies to inference only — eval mode, grad
-        disabled, GPU input — when the decoder runs the native GRU kernel and
-        all heads together fit its two 16-wide output tiles."""
+        disabled — when the native kernel does."""
         if not self.cfg.fused_head_decode or self.training:
             return False
-        if torch.is_grad_enabled() or not enc.is_cuda:
-            return False
-        if not gru_kernel_supports(self.cfg.hidden, comp.shape[0]):
-            return False
-        return len(self.heads) * len(self.cfg.quantiles) <= HEAD_FUSE_MAX_OUT
+        return not torch.is_grad_enabled() and self._native_heads_fit(enc, comp)
+
+    def _head_weight_of_dir(self, w_all: torch.Tensor, d: int) -> torch.Tensor:
+        """Direction d's contiguous (R*Q, H) slice of the concatenated head
+        weights."""
+        H = self.cfg.hidden
+        return w_all[:, d * H : (d + 1) * H].contiguous()
 
     def _head_weights_per_dir(self) -> List[torch.Tensor]:
-        H = self.cfg.hidden
         w_all = self._head_weights()
-        dirs = 2 if self.cfg.bidirectional else 1
-        return [w_all[:, d * H : (d + 1) * H].contiguous() for d in range(dirs)]
+        return [self._head_weight_of_dir(w_all, d)
+                for d in range(self.decoder.dirs)]
 
     def _encode_fused(self, x: torch.Tensor,
                       kv_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -564,21 +541,17 @@ class DeepRestNet(nn.Module):
         h = self.layers[0].ln1(x)
         for i, layer in enumerate(self.layers):
             next_ln = self.layers[i + 1].ln1 if i + 1 < n else None
-            if kv_lengths is None:
-                x, h = layer.forward_fused(x, h, next_ln)
-            else:
-                x, h = layer.forward_fused(x, h, next_ln, kv_lengths)
+            x, h = layer.forward_fused(x, h, next_ln, kv_lengths)
         return x
 
     def _apply_heads(self, h_dirs) -> torch.Tensor:
         """Per-resource heads as a sum of per-direction GEMMs (no concat),
         each with a batched-K backward (ops/linear_bigk.py)."""
-        H = self.cfg.hidden
         w_all = self._head_weights()
         out = None
         for d, h_d in enumerate(h_dirs):
             h_d = self.dropout(h_d)
-            part = bigk_linear(h_d, w_all[:, d * H : (d + 1) * H].contiguous())
+            part = bigk_linear(h_d, self._head_weight_of_dir(w_all, d))
             out = part if out is None else out + part
         return self._finish_heads(out)
 
@@ -623,22 +596,9 @@ class DeepRestNet(nn.Module):
         cfg = self.cfg
         dec = self.decoder
         comp = self.graph()
-        C = comp.shape[0]
-        H = dec.hidden
-        dev, dt = traffic.device, traffic.dtype
 
         bounds = list(range(0, T_total, chunk_size)) + [T_total]
         chunks = list(zip(bounds[:-1], bounds[1:]))
-
-        def encode(x):
-            x = self.in_proj(x)
-            x = x + self._pos_encoding(x.shape[1], x.device, x.dtype)
-            x = self.in_norm(x)
-            if cfg.fused_residual_norm:
-                return self._encode_fused(x)
-            for layer in self.layers:
-                x = layer(x)
-            return x
 
         # fp8 MFMA decode (BASELINE config 5) applies to the long-horizon
         # path exactly as to forward()
@@ -648,48 +608,37 @@ class DeepRestNet(nn.Module):
         use_dec = self._use_head_decode(traffic, comp)
         w_dirs = self._head_weights_per_dir() if use_dec else None
 
-        # forward sweep
-        h_f = torch.tanh(dec.h0_proj(comp)).unsqueeze(0).expand(B, C, H).contiguous().to(dt)
-        gamma = dec.cond_gamma(comp)
-        beta = dec.cond_beta(comp)
-        fwd_outs = []
-        enc_cache = []
-        for (s, e) in chunks:
-            enc = encode(traffic[:, s:e])
-            enc_cache.append(enc)
-            xg = dec.x_proj(enc)
-            if use_dec:
-                part, h_f = fused_gru_decode(xg, dec.w_hh, dec.b_hh, h_f, gamma,
-                                             beta, w_dirs[0], reverse=False,
-                                             fp8=fp8)
-                fwd_outs.append(part)
-                continue
-            out = fused_gru_sequence(xg, dec.w_hh, dec.b_hh, h_f, gamma, beta,
-                                     reverse=False, fp8=fp8)
-            h_f = out[:, -1].contiguous()
-            fwd_outs.append(out)
+        enc_cache = [None] * len(chunks)
 
-        if cfg.bidirectional:
-            gamma_r = dec.cond_gamma_r(comp)
-            beta_r = dec.cond_beta_r(comp)
-            h_r = torch.tanh(dec.h0_proj_r(comp)).unsqueeze(0).expand(B, C, H).contiguous().to(dt)
-            rev_outs = [None] * len(chunks)
-            for ci in range(len(chunks) - 1, -1, -1):
-                xg_r = dec.x_proj_r(enc_cache[ci])
+        def sweep(d):
+            """Direction d over all chunks, left->right for d = 0 (encoding
+            each chunk on the way) and right->left for d = 1, the state
+            carried from chunk to chunk; returns the per-chunk outputs."""
+            # launch order kept stable: the forward sweep builds its initial
+            # state before the FiLM pair, the reverse sweep after it
+            if d == 0:
+                h = dec.h0(comp, B, d).to(traffic.dtype)
+            gamma, beta = dec.film(comp, d)
+            if d == 1:
+                h = dec.h0(comp, B, d).to(traffic.dtype)
+            w_hh, b_hh = dec._of("w_hh", d), dec._of("b_hh", d)
+            outs = [None] * len(chunks)
+            for ci in (reversed(range(len(chunks))) if d else range(len(chunks))):
+                if enc_cache[ci] is None:
+                    s, e = chunks[ci]
+                    enc_cache[ci] = self._encode(traffic[:, s:e])
+                xg = dec.x_gates(enc_cache[ci], d)
                 if use_dec:
-                    part, h_r = fused_gru_decode(xg_r, dec.w_hh_r, dec.b_hh_r,
-                                                 h_r, gamma_r, beta_r, w_dirs[1],
-                                                 reverse=True, fp8=fp8)
-                    rev_outs[ci] = part
+                    outs[ci], h = fused_gru_decode(xg, w_hh, b_hh, h, gamma, beta,
+                                                   w_dirs[d], reverse=bool(d),
+                                                   fp8=fp8)
                     continue
-                out_r = fused_gru_sequence(xg_r, dec.w_hh_r, dec.b_hh_r, h_r,
-                                           gamma_r, beta_r, reverse=True,
-                                           fp8=fp8)
-                h_r = out_r[:, 0].contiguous()
-                rev_outs[ci] = out_r
-            h_chunks = list(zip(fwd_outs, rev_outs))
-        else:
-            h_chunks = [(f,) for f in fwd_outs]
+                outs[ci] = fused_gru_sequence(xg, w_hh, b_hh, h, gamma, beta,
+                                              reverse=bool(d), fp8=fp8)
+                h = outs[ci][:, 0 if d else -1].contiguous()
+            return outs
+
+        h_chunks = list(zip(*[sweep(d) for d in range(dec.dirs)]))
 
         if use_dec:
             preds = [self._finish_heads(sum(parts[1:], parts[0]))

@@ -266,6 +266,28 @@ def gru_kernel_supports(H: int, C: int) -> bool:
     return H == 128 and C >= 3
 
 
+def _fuses_heads(x_gates, h0, w_head) -> bool:
+    """The native kernel applies and the heads fit its one K=32 MFMA step
+    (backward) / two 16-wide output tiles (decode)."""
+    return (x_gates.is_cuda and gru_kernel_supports(h0.shape[2], h0.shape[1])
+            and w_head.shape[0] <= HEAD_FUSE_MAX_OUT)
+
+
+def _kernel_operands(x_gates, w_hh, b_hh, h0, gamma, beta):
+    """The six operands as the kernel entries take them: contiguous, in
+    x_gates' dtype, b_hh in fp32.  Called outside the autograd Functions so
+    the casts are tracked back to the fp32 master parameters."""
+    dt = x_gates.dtype
+    return (
+        x_gates.contiguous(),
+        w_hh.to(dt).contiguous(),
+        b_hh.float().contiguous(),
+        h0.to(dt).contiguous(),
+        gamma.to(dt).contiguous(),
+        beta.to(dt).contiguous(),
+    )
+
+
 def fused_gru_sequence(
     x_gates: torch.Tensor,
     w_hh: torch.Tensor,
@@ -303,14 +325,7 @@ def fused_gru_sequence(
             beta = torch.zeros(C, G, device=x_gates.device, dtype=dt)
         elif beta is None:
             beta = torch.zeros_like(gamma)
-        args = (
-            x_gates.contiguous(),
-            w_hh.to(dt).contiguous(),
-            b_hh.float().contiguous(),
-            h0.to(dt).contiguous(),
-            gamma.to(dt).contiguous(),
-            beta.to(dt).contiguous(),
-        )
+        args = _kernel_operands(x_gates, w_hh, b_hh, h0, gamma, beta)
         if fp8:
             # fp8 MFMA path is inference-only (BASELINE config 5): the
             # recurrent GEMM runs on e4m3 tiles, state stays fp32 in-kernel
@@ -321,8 +336,6 @@ def fused_gru_sequence(
             ext = require_native("fused_gru_sequence")
             h_all, _ = ext.gru_seq_forward(*args, reverse, False, True)
             return h_all
-        # dtype harmonization outside the Function so the casts are
-        # autograd-tracked back to the fp32 master parameters
         return _FusedGRUSequence.apply(*args, reverse)
     return reference_gru_sequence(x_gates, w_hh, b_hh, h0, gamma, beta, reverse)
 
@@ -344,25 +357,13 @@ def fused_gru_heads(
     autograd node whose backward hands the O-wide ``grad_part`` straight to
     the kernel.  Everywhere else (CPU, off-spec shapes, wider heads) it is
     the differentiable composition of the two ops."""
-    O = w_head.shape[0]
-    native = (x_gates.is_cuda and gru_kernel_supports(h0.shape[2], h0.shape[1])
-              and O <= HEAD_FUSE_MAX_OUT)
-    if not native:
+    if not _fuses_heads(x_gates, h0, w_head):
         h_all = fused_gru_sequence(x_gates, w_hh, b_hh, h0, gamma, beta, reverse)
         return torch.nn.functional.linear(h_all, w_head.to(h_all.dtype))
-    dt = x_gates.dtype
-    # dtype harmonization outside the Function (autograd-tracked casts);
     # w_head keeps its dtype so its gradient leaves the fp32 sum unrounded
     return _FusedGRUHeads.apply(
-        x_gates.contiguous(),
-        w_hh.to(dt).contiguous(),
-        b_hh.float().contiguous(),
-        h0.to(dt).contiguous(),
-        gamma.to(dt).contiguous(),
-        beta.to(dt).contiguous(),
-        w_head.contiguous(),
-        reverse,
-    )
+        *_kernel_operands(x_gates, w_hh, b_hh, h0, gamma, beta),
+        w_head.contiguous(), reverse)
 
 
 def fused_gru_decode(
@@ -400,34 +401,26 @@ def fused_gru_decode(
         for t in (x_gates, w_hh, b_hh, h0, gamma, beta, w_head)
     ):
         raise RuntimeError("fused_gru_decode is inference-only (no autograd)")
-    O = w_head.shape[0]
-    native = (x_gates.is_cuda and gru_kernel_supports(h0.shape[2], h0.shape[1])
-              and O <= HEAD_FUSE_MAX_OUT)
-    if not native and lengths is not None:
-        h_all, h_last = reference_gru_sequence(
-            x_gates, w_hh, b_hh, h0, gamma, beta, reverse, lengths=lengths,
-            return_state=True)
-        # padded h_all rows are zero and the heads have no bias: out is too
+    if not _fuses_heads(x_gates, h0, w_head):
+        if lengths is not None:
+            h_all, h_last = reference_gru_sequence(
+                x_gates, w_hh, b_hh, h0, gamma, beta, reverse, lengths=lengths,
+                return_state=True)
+        else:
+            h_all = fused_gru_sequence(x_gates, w_hh, b_hh, h0, gamma, beta,
+                                       reverse, fp8=fp8)
+            h_last = h_all[:, 0 if reverse else -1]
+        # with lengths: padded h_all rows are zero and the heads have no
+        # bias, so out is zero there too
         out = torch.nn.functional.linear(h_all, w_head.to(h_all.dtype))
         return out, h_last
-    if not native:
-        h_all = fused_gru_sequence(x_gates, w_hh, b_hh, h0, gamma, beta,
-                                   reverse, fp8=fp8)
-        out = torch.nn.functional.linear(h_all, w_head.to(h_all.dtype))
-        return out, h_all[:, 0 if reverse else -1]
     ext = require_native("fused_gru_decode")
-    dt = x_gates.dtype
+    O = w_head.shape[0]
     # (32, H) bf16 B-operand image: w_head zero-padded along the output axis
     wh_fwd = torch.zeros(32, w_head.shape[1], device=x_gates.device,
                          dtype=torch.bfloat16)
     wh_fwd[:O] = w_head
     out, h_last = ext.gru_seq_decode(
-        x_gates.contiguous(),
-        w_hh.to(dt).contiguous(),
-        b_hh.float().contiguous(),
-        h0.to(dt).contiguous(),
-        gamma.to(dt).contiguous(),
-        beta.to(dt).contiguous(),
-        wh_fwd, O, bool(reverse), bool(fp8), lengths,
-    )
+        *_kernel_operands(x_gates, w_hh, b_hh, h0, gamma, beta),
+        wh_fwd, O, bool(reverse), bool(fp8), lengths)
     return out, h_last

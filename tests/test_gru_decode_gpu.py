@@ -199,7 +199,9 @@ def test_raises_when_grad_is_required(dev):
 
 def test_binding_rejects_bad_head_images(dev):
     """The kernel entry refuses an O its two N-tiles cannot hold and a weight
-    image of the wrong shape or dtype (it would read outside the image)."""
+    image of the wrong shape or dtype (it would read outside the image); both
+    forward entries refuse operands whose shapes or device do not match
+    x_gates."""
     from deeprest_amd.ops.native import require_native
 
     ext = require_native("test")
@@ -211,6 +213,24 @@ def test_binding_rejects_bad_head_images(dev):
                            (img.float(), 9)]:
         with pytest.raises(RuntimeError):
             ext.gru_seq_decode(*args, bad_img, bad_o, False, False)
+
+    # the sequence entry shares the decode entry's operand checks: a short
+    # h0 / beta / b_hh or a host tensor never reaches the kernel
+    B, T, C = 2, 3, 3
+    good = dict(zip(("xg", "w_hh", "b_hh", "h0", "gamma", "beta"), (
+        t.to(dev) for t in _inputs((B, T, C, 9), torch.float32)[:6])))
+    bad_operands = {
+        "h0 of batch B + 1": {"h0": torch.cat([good["h0"], good["h0"][:1]])},
+        "beta one row short": {"beta": good["beta"][:-1].contiguous()},
+        "b_hh of 3H - 1": {"b_hh": good["b_hh"][:-1].contiguous()},
+        "h0 on the host": {"h0": good["h0"].cpu()},
+    }
+    for what, swap in bad_operands.items():
+        print("gru_seq_forward with", what)
+        with pytest.raises(RuntimeError):
+            ext.gru_seq_forward(*{**good, **swap}.values(), False, False)
+    h_all, _ = ext.gru_seq_forward(*good.values(), False, False)
+    assert h_all.shape == (B, T, C, H)
 
 
 # -------------------------------------------------------------------- model
