@@ -144,7 +144,7 @@ def cmd_collect(args):
         if not promql:
             raise SystemExit(f"--query needs resource=promql, got {spec!r}")
         queries[resource] = promql
-    collector = Collector(window_sec=args.interval)
+    collector = Collector(window_sec=args.interval, missing=args.missing)
     poller = CollectionPoller(
         collector,
         jaeger_url=args.jaeger,
@@ -217,6 +217,10 @@ def main(argv=None):
     c.add_argument("--duration", type=float, default=None)
     c.add_argument("--max-polls", type=int, default=None)
     c.add_argument("--out", default="raw_data.pkl")
+    c.add_argument("--missing", choices=["carry", "nan"], default="carry",
+                   help="value of a metric in a window without a sample: the "
+                        "last one seen (carry) or NaN = not observed, which "
+                        "training masks out (nan)")
 
     v = sub.add_parser("serve")
     v.add_argument("--checkpoint", default=None)

@@ -36,6 +36,15 @@ void dr_pinball_fwd(const void* out, const float* labels, const float* quantiles
 void dr_pinball_bwd(const void* out, const float* labels, const float* quantiles,
                     int Q, int64_t N, const float* grad_loss, float inv_n,
                     void* dout, int is_bf16, hipStream_t stream);
+int dr_pinball_masked_slots(int M);
+void dr_pinball_masked_fwd(const void* out, const float* labels,
+                           const float* quantiles, int Q, int64_t R, int M,
+                           float* wsum, int* wcnt, float* loss, float* w,
+                           int is_bf16, hipStream_t stream);
+void dr_pinball_masked_bwd(const void* out, const float* labels,
+                           const float* quantiles, int Q, int64_t R, int M,
+                           const float* grad_loss, const float* w, void* dout,
+                           int is_bf16, hipStream_t stream);
 void dr_fused_adam(const int64_t* meta, int nt, int64_t total, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int step,
                    hipStream_t stream);
@@ -305,6 +314,84 @@ at::Tensor pinball_backward(at::Tensor grad, at::Tensor outputs, at::Tensor labe
   dr_pinball_bwd(outputs.data_ptr(), labels.data_ptr<float>(),
                  q.data_ptr<float>(), Q, N, gc.data_ptr<float>(), inv_n,
                  dout.data_ptr(), is_bf16(outputs), cur_stream());
+  return dout;
+}
+
+// Masked variant: a non-finite label is "not observed".  outputs (..., M, Q),
+// labels (..., M).  Returns {loss, w}: w (M,) f32 holds each metric's gradient
+// weight 1/(Mp*cnt[m]) (0 for a metric with no present label), which the
+// backward reads on the device.  No host sync: the mask may change between
+// replays of a captured graph.
+struct MaskedShape {
+  int Q, M;
+  int64_t R;
+};
+
+static MaskedShape pinball_masked_checks(const at::Tensor& outputs,
+                                         const at::Tensor& labels,
+                                         const at::Tensor& q) {
+  check_dtype(outputs, "pinball outputs");
+  TORCH_CHECK(labels.scalar_type() == at::kFloat, "pinball labels must be f32");
+  TORCH_CHECK(outputs.is_contiguous() && labels.is_contiguous());
+  TORCH_CHECK(outputs.is_cuda() && labels.device() == outputs.device() &&
+                  q.device() == outputs.device(),
+              "pinball operands must all be on the outputs' GPU");
+  TORCH_CHECK(outputs.dim() >= 2 && labels.dim() == outputs.dim() - 1,
+              "masked pinball wants outputs (..., M, Q) and labels (..., M)");
+  MaskedShape s;
+  s.Q = (int)outputs.size(-1);
+  TORCH_CHECK(s.Q <= 8, "at most 8 quantiles");
+  TORCH_CHECK(q.scalar_type() == at::kFloat && q.is_contiguous() &&
+                  q.numel() == s.Q,
+              "quantiles must be a contiguous f32 tensor with one entry per output");
+  TORCH_CHECK(outputs.size(-2) < (1LL << 31), "too many metrics");
+  s.M = (int)outputs.size(-2);
+  TORCH_CHECK(labels.size(-1) == s.M && labels.numel() * s.Q == outputs.numel(),
+              "labels do not match outputs");
+  s.R = s.M > 0 ? labels.numel() / s.M : 0;
+  TORCH_CHECK(s.R < (1LL << 31), "per-metric counts are int32: B*T must be < 2^31");
+  return s;
+}
+
+std::vector<at::Tensor> pinball_masked_forward(at::Tensor outputs, at::Tensor labels,
+                                               at::Tensor q) {
+  const at::cuda::CUDAGuard guard(outputs.device());
+  const MaskedShape s = pinball_masked_checks(outputs, labels, q);
+  auto f32 = outputs.options().dtype(at::kFloat);
+  if (s.R == 0 || s.M == 0 || s.Q == 0)
+    return {at::zeros({}, f32), at::zeros({s.M}, f32)};
+  // the finalize launch writes the loss and every w[m]
+  auto loss = at::empty({}, f32);
+  auto w = at::empty({s.M}, f32);
+  // [0]: per-metric fp32 sums (zero bits are 0.0f), [1]: int counts; `slots`
+  // copies of each, which the finalize launch adds up
+  const int64_t slots = dr_pinball_masked_slots(s.M);
+  auto ws = at::zeros({2, slots, s.M}, outputs.options().dtype(at::kInt));
+  int* cnt = ws.data_ptr<int>() + slots * s.M;
+  dr_pinball_masked_fwd(outputs.data_ptr(), labels.data_ptr<float>(),
+                        q.data_ptr<float>(), s.Q, s.R, s.M,
+                        reinterpret_cast<float*>(ws.data_ptr<int>()), cnt,
+                        loss.data_ptr<float>(), w.data_ptr<float>(),
+                        is_bf16(outputs), cur_stream());
+  return {loss, w};
+}
+
+at::Tensor pinball_masked_backward(at::Tensor grad, at::Tensor outputs,
+                                   at::Tensor labels, at::Tensor q, at::Tensor w) {
+  const at::cuda::CUDAGuard guard(outputs.device());
+  const MaskedShape s = pinball_masked_checks(outputs, labels, q);
+  TORCH_CHECK(grad.is_cuda() && grad.scalar_type() == at::kFloat && grad.numel() == 1,
+              "pinball grad must be a scalar f32 CUDA tensor");
+  TORCH_CHECK(w.scalar_type() == at::kFloat && w.is_contiguous() &&
+                  w.device() == outputs.device() && w.numel() == s.M,
+              "w must be the (M,) f32 weights of pinball_masked_forward");
+  auto dout = at::empty_like(outputs);
+  if (s.R == 0 || s.M == 0 || s.Q == 0) return dout;
+  auto gc = grad.contiguous();
+  dr_pinball_masked_bwd(outputs.data_ptr(), labels.data_ptr<float>(),
+                        q.data_ptr<float>(), s.Q, s.R, s.M, gc.data_ptr<float>(),
+                        w.data_ptr<float>(), dout.data_ptr(), is_bf16(outputs),
+                        cur_stream());
   return dout;
 }
 
@@ -631,6 +718,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rstd"), py::arg("seed"), py::arg("p"));
   m.def("pinball_forward", &pinball_forward);
   m.def("pinball_backward", &pinball_backward);
+  m.def("pinball_masked_forward", &pinball_masked_forward);
+  m.def("pinball_masked_backward", &pinball_masked_backward);
   m.def("fused_adam", &fused_adam);
   m.def("fused_adam_capturable", &fused_adam_capturable);
   m.def("gru_seq_forward", &gru_seq_forward, py::arg("xg"), py::arg("w_hh"),

@@ -77,11 +77,25 @@ def trace_start_time(trace: Dict[str, Any]) -> float:
 
 class Collector:
     """Accumulates Jaeger traces and Prometheus samples; emits contract
-    windows discretized on the scrape interval."""
+    windows discretized on the scrape interval.
 
-    def __init__(self, window_sec: float = 5.0, t0: Optional[float] = None) -> None:
+    ``missing`` says what a window reports for a (component, resource) key
+    that received no sample in it (a failed scrape, a restarted pod, a
+    component deployed half-way through the recording):
+
+    - ``"carry"``: the last seen value, 0.0 before the first observation;
+    - ``"nan"``: ``float("nan")`` — "not observed", in every such window,
+      those before the first observation included.  Training masks these
+      labels out instead of learning from invented ones.
+    """
+
+    def __init__(self, window_sec: float = 5.0, t0: Optional[float] = None,
+                 missing: str = "carry") -> None:
+        if missing not in ("carry", "nan"):
+            raise ValueError(f"missing must be 'carry' or 'nan', got {missing!r}")
         self.window_sec = window_sec
         self.t0 = t0
+        self.missing = missing
         self._traces: List[Tuple[float, Dict[str, Any]]] = []
         self._samples: List[Dict[str, Any]] = []
 
@@ -128,6 +142,7 @@ class Collector:
 
         # metric identity must appear in EVERY window (featurizer requirement):
         # carry the last seen value forward, 0.0 before first observation
+        # (missing="carry"), or report NaN where nothing was sampled
         all_keys: List[Tuple[str, str]] = []
         seen = set()
         for w in range(n_win):
@@ -139,6 +154,8 @@ class Collector:
         out = []
         last: Dict[Tuple[str, str], float] = {k: 0.0 for k in all_keys}
         for w in range(n_win):
+            if self.missing == "nan":
+                last = {k: float("nan") for k in all_keys}
             for key, val in win_metrics.get(w, {}).items():
                 last[key] = val
             metrics = [

@@ -14,6 +14,11 @@ where a span tree is
 We keep that format byte-compatible (plain dicts/lists pickled) and add a
 typed in-memory view on top of it.  Everything downstream (featurizer,
 synthesizer, trainer, REST ingestion) speaks this contract.
+
+A metric's ``value`` may be ``float("nan")``: the metric was NOT OBSERVED in
+that window (a failed scrape, a component that was down).  The metric still
+appears in every window — NaN is the marker, there is no separate mask — and
+training neither learns from nor is scored on such a label.
 """
 
 from __future__ import annotations
@@ -120,6 +125,8 @@ def validate_raw_data(raw_data: Any) -> None:
     """Validate the plain-dict raw-data structure; raise ContractError on issues.
 
     Mirrors the reference input format (resource-estimation/README.md:29-63).
+    A NaN metric value is valid and means "not observed in this window";
+    non-numeric values are rejected.
     """
     if not isinstance(raw_data, (list, tuple)):
         raise ContractError(f"raw_data must be a list, got {type(raw_data).__name__}")

@@ -17,7 +17,9 @@ configurable generator that emits data in the raw-data contract:
   causality can actually fit it;
 - anomaly injection (utilization NOT justified by traffic) for the
   sanity-check capability (reference README.md:3: ransomware/cryptojacking
-  detection).
+  detection);
+- missing-sample injection (``inject_missing``: bursts of NaN = "not
+  observed" labels, the holes of real scrape data).
 
 Two output paths:
 - ``generate_raw()``   — full span trees in the contract format (tests,
@@ -412,3 +414,48 @@ class SyntheticApp:
         baseline = float(np.median(series))
         series[start : start + length] += magnitude * max(baseline, 1.0)
         return data
+
+
+def inject_missing(
+    data: FeaturizedData,
+    rate: float,
+    mean_gap: float = 8.0,
+    seed: int = 0,
+    metrics: Optional[Sequence[str]] = None,
+) -> FeaturizedData:
+    """Knock bursts of samples out of the resource series in-place (NaN = not
+    observed), the way scrape data has holes: failed scrapes, restarted pods.
+
+    Per metric the timeline alternates observed runs and gaps.  Gap lengths are
+    geometric with mean ``mean_gap`` windows, observed runs geometric with mean
+    ``mean_gap * (1 - rate) / rate``, so the expected missing share is
+    ``rate``.  Each metric draws from its own stream derived from ``seed`` and
+    its position, so the pattern is deterministic by seed and independent of
+    which other metrics are selected.  ``metrics``: names to affect (default:
+    all).  Traffic is untouched.
+    """
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"rate must be in [0, 1), got {rate}")
+    if mean_gap < 1.0:
+        raise ValueError(f"mean_gap must be >= 1, got {mean_gap}")
+    names = list(data.resources) if metrics is None else list(metrics)
+    if rate == 0.0:
+        return data
+    order = {n: i for i, n in enumerate(data.resources)}
+    mean_run = max(mean_gap * (1.0 - rate) / rate, 1.0)
+    for name in names:
+        series = np.asarray(data.resources[name], dtype=np.float64)
+        rng = np.random.default_rng([seed, order[name]])
+        T = len(series)
+        gone = np.zeros(T, dtype=bool)
+        missing = bool(rng.random() < rate)
+        t = 0
+        while t < T:
+            n = int(rng.geometric(1.0 / (mean_gap if missing else mean_run)))
+            if missing:
+                gone[t : t + n] = True
+            t += n
+            missing = not missing
+        series[gone] = np.nan
+        data.resources[name] = series
+    return data

@@ -14,7 +14,7 @@ reference they live only in process memory.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -39,10 +39,39 @@ def sliding_window(ts: np.ndarray, window_size: int) -> np.ndarray:
     return out
 
 
-def minmax_fit(M: np.ndarray, split: int) -> Tuple[float, float]:
-    """(min, max) over the first `split` entries (train portion)."""
+def minmax_fit(M: np.ndarray, split: int,
+               name: Optional[str] = None) -> Tuple[float, float]:
+    """(min, max) over the first `split` entries (train portion).
+
+    NaN means "not observed" and is ignored.  A train portion with nothing
+    observed cannot be scaled: ValueError naming the series (``name``).
+    """
     train = M[:split]
-    return float(np.min(train)), float(np.max(train))
+    lo, hi = float(np.min(train)), float(np.max(train))
+    if lo != lo or hi != hi:                 # NaN present: fit the observed
+        if np.isnan(train).all():
+            raise ValueError(
+                f"series {name if name is not None else '<unnamed>'!r} has no "
+                f"observed (finite) value in its train split")
+        lo, hi = float(np.nanmin(train)), float(np.nanmax(train))
+    return lo, hi
+
+
+def forward_fill(series: np.ndarray) -> np.ndarray:
+    """Last observation carried forward along axis 0 (NaN = not observed); a
+    leading gap takes the first observation.  A column with no observation
+    stays NaN.  Returns a new array of the same shape."""
+    a = np.asarray(series)
+    if a.ndim == 0 or len(a) == 0:
+        return np.array(a, copy=True)
+    flat = a.reshape(len(a), -1)
+    obs = ~np.isnan(flat)
+    rows = np.arange(len(flat))[:, None]
+    last = np.maximum.accumulate(np.where(obs, rows, -1), axis=0)
+    first = np.argmax(obs, axis=0)            # 0 for an all-NaN column
+    idx = np.where(last >= 0, last, first[None, :])
+    out = np.take_along_axis(flat, idx, axis=0)
+    return out.reshape(a.shape)
 
 
 def minmax_apply(M: np.ndarray, min_val: float, max_val: float) -> np.ndarray:
@@ -63,8 +92,9 @@ class MinMaxScaler:
     def scale(self) -> float:
         return self.max_val - self.min_val
 
-    def fit(self, M: np.ndarray, split: int) -> "MinMaxScaler":
-        self.min_val, self.max_val = minmax_fit(M, split)
+    def fit(self, M: np.ndarray, split: int,
+            name: Optional[str] = None) -> "MinMaxScaler":
+        self.min_val, self.max_val = minmax_fit(M, split, name)
         return self
 
     def transform(self, M: np.ndarray) -> np.ndarray:

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ..data.featurize import FeaturizedData
-from ..data.windows import MinMaxScaler, sliding_window
+from ..data.windows import MinMaxScaler, forward_fill, sliding_window
 
 
 class EstimationDataset:
@@ -51,6 +51,10 @@ class EstimationDataset:
         traffic = np.asarray(data.traffic, dtype=np.float32)
         y_flat = np.stack([data.resources[n] for n in self.metric_names], axis=-1)
 
+        # NaN labels = "not observed" (data/contract.py): they survive
+        # windowing, log1p and scaling, and the loss masks them out
+        self.has_missing = bool(np.isnan(y_flat).any())
+
         X = sliding_window(traffic, step_size)                 # (N, T, P) f32
         y = sliding_window(y_flat.astype(np.float64), step_size)  # (N, T, M)
         self.num_windows = len(X)
@@ -73,12 +77,29 @@ class EstimationDataset:
             X *= np.float32(1.0 / self.x_scaler.scale)
         self.y_scalers: List[MinMaxScaler] = []
         for idx in range(y.shape[-1]):
-            sc = MinMaxScaler().fit(y[:, :, idx], self.split)
+            sc = MinMaxScaler().fit(y[:, :, idx], self.split,
+                                    name=self.metric_names[idx])
             y[:, :, idx] = sc.transform(y[:, :, idx])
             self.y_scalers.append(sc)
 
         self.X = torch.from_numpy(X)                           # already f32 contiguous
         self.y = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))
+
+        # dense labels for consumers that cannot take holes (the baselines,
+        # the ridge residual base): last observation carried forward along
+        # the timeline.  Without holes they ARE the arrays above.
+        self.y_raw_filled = self.y_raw
+        self.y_filled = self.y
+        if self.has_missing:
+            filled = sliding_window(
+                forward_fill(y_flat.astype(np.float64)), step_size)
+            self.y_raw_filled = filled.copy()
+            if target_transform == "log1p":
+                filled = np.log1p(np.maximum(filled, 0.0))
+            for idx, sc in enumerate(self.y_scalers):
+                filled[:, :, idx] = sc.transform(filled[:, :, idx])
+            self.y_filled = torch.from_numpy(
+                np.ascontiguousarray(filled, dtype=np.float32))
 
     # ------------------------------------------------------------------ views
     @property

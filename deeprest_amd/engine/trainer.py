@@ -109,9 +109,15 @@ class Trainer:
         self.autocast_dtype = (
             torch.bfloat16 if self.cfg.train.dtype == "bf16" else torch.float32
         )
+        # labels with holes (NaN = not observed): the masked loss everywhere,
+        # dense forward-filled labels only where a fit cannot take holes
+        self._missing = self.dataset.has_missing
+        net = self.model
         # THE training step — shared verbatim with bench.py (engine/step.py)
         self.step = TrainStep(
             self.model, self.optimizer, dist_ctx=self.dist,
+            loss_fn=(lambda out, yb: net.loss(out, yb, missing=True))
+            if self._missing else None,
             autocast_dtype=self.autocast_dtype
             if self.device.type == "cuda" else None,
         )
@@ -128,7 +134,10 @@ class Trainer:
         M = ds.y.shape[-1]
         Xf = X[: ds.split].reshape(-1, P).astype(np.float64)
         Xf = np.concatenate([Xf, np.ones((len(Xf), 1))], axis=1)
-        yf = ds.y[: ds.split].numpy().reshape(-1, M).astype(np.float64)
+        # fit on the forward-filled labels (y itself when nothing is missing);
+        # the residual TARGET stays y - ridge, so NaN survives and the net
+        # never trains on a filled value
+        yf = ds.y_filled[: ds.split].numpy().reshape(-1, M).astype(np.float64)
         A = Xf.T @ Xf + 1e-3 * np.eye(P + 1)
         self._ridge_w = np.linalg.solve(A, Xf.T @ yf)          # (P+1, M)
         self._ridge_norm = self.ridge_apply(X).astype(np.float32)
@@ -154,7 +163,9 @@ class Trainer:
         # GPU when present; 39 sequential CPU fits took 74 s)
         from ..models.baselines import ResourceAwareBatchBaseline
 
-        y_stack = np.ascontiguousarray(np.moveaxis(ds.y_raw, -1, 0))  # (M, N, T)
+        # the baselines fit on dense labels (y_raw itself without holes)
+        y_raw = ds.y_raw_filled
+        y_stack = np.ascontiguousarray(np.moveaxis(y_raw, -1, 0))  # (M, N, T)
         resrc_all = ResourceAwareBatchBaseline(
             split=ds.split, window=ds.step_size,
             epochs=t_cfg.baseline_epochs, seed=t_cfg.seed,
@@ -162,7 +173,7 @@ class Trainer:
         ).fit_and_estimate(y_stack)                         # (M, N_test, T)
         comp_list = []
         for idx, name in enumerate(ds.metric_names):
-            yw = ds.y_raw[:, :, idx]
+            yw = y_raw[:, :, idx]
             comp_name = self.model.spec.components[self.model.spec.comp_of[idx]]
             comp = ComponentAwareBaseline(
                 component=comp_name, invocations=ds.data.invocations,
@@ -315,6 +326,10 @@ class Trainer:
         for m in range(M):
             s = np.maximum(band[:, :, m, 0] - yb[:, :, m],
                            yb[:, :, m] - band[:, :, m, Q - 1]).ravel()
+            if self._missing:
+                s = s[~np.isnan(s)]          # observed entries only
+                if len(s) == 0:
+                    continue                 # nothing to calibrate on: offset 0
             n = len(s)
             q = min((np.ceil((n + 1) * (1.0 - alpha)) / n), 1.0)
             offs[m] = np.quantile(s, q)
@@ -342,7 +357,7 @@ class Trainer:
             ridge = torch.from_numpy(
                 self._ridge_norm[ds.split :][eval_idx]).to(self.device)
             out = out + ridge.unsqueeze(-1)
-        test_loss = float(self.model.loss(out, yb).item())
+        test_loss = float(self.model.loss(out, yb, missing=self._missing).item())
 
         outputs = np.maximum(out.cpu().numpy(), 1e-6)      # (K, T, M, Q)
         labels = yb.cpu().numpy()
@@ -353,10 +368,14 @@ class Trainer:
         for m, name in enumerate(ds.metric_names):
             labels_d = ds.denormalize_metric(labels[:, :, m], m).ravel()
             pred_d = ds.denormalize_metric(outputs[:, :, m, median_q], m).ravel()
+            # score observed entries only (all of them without holes)
+            obs = ~np.isnan(labels_d) if self._missing else slice(None)
+            labels_d = labels_d[obs]
+            pred_d = pred_d[obs]
             per_est = {}
             if baselines is not None:
                 for est_name, key in (("resrc", "resrc"), ("comp", "comp")):
-                    bl = baselines[key][eval_idx][:, :, m].ravel()
+                    bl = baselines[key][eval_idx][:, :, m].ravel()[obs]
                     per_est[est_name] = error_percentiles(np.abs(bl - labels_d))
             per_est["deepr"] = error_percentiles(np.abs(pred_d - labels_d))
             tables[name] = per_est
@@ -372,8 +391,8 @@ class Trainer:
                     band[:, :, -1] + self._conformal[m], band[:, :, -2])
             coverage[name] = quantile_coverage(
                 labels_d,
-                ds.denormalize_metric(band[:, :, 0], m).ravel(),
-                ds.denormalize_metric(band[:, :, Q - 1], m).ravel())
+                ds.denormalize_metric(band[:, :, 0], m).ravel()[obs],
+                ds.denormalize_metric(band[:, :, Q - 1], m).ravel()[obs])
         self.last_coverage = coverage
         return test_loss, tables
 

@@ -36,8 +36,8 @@ import torch.nn.functional as F
 
 from ..data.featurize import FeaturizedData
 from ..ops import (dropout_add, dropout_add_layer_norm, fused_gru_decode,
-                   fused_gru_heads, fused_gru_sequence, layer_norm, mha_forward,
-                   pinball_loss)
+                   fused_gru_heads, fused_gru_sequence, layer_norm,
+                   masked_pinball_loss, mha_forward, pinball_loss)
 from ..ops.gru import HEAD_FUSE_MAX_OUT, gru_kernel_supports
 from ..ops.linear_bigk import bigk_linear
 
@@ -570,7 +570,12 @@ class DeepRestNet(nn.Module):
             preds = outs[:, :, self.comp_of, self.res_of, :]  # (B, T, M, Q)
         return preds + self.metric_bias
 
-    def loss(self, outputs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def loss(self, outputs: torch.Tensor, labels: torch.Tensor,
+             missing: bool = False) -> torch.Tensor:
+        """``missing=True``: NaN labels are "not observed" and the loss is the
+        mean of per-metric means over the observed entries."""
+        if missing:
+            return masked_pinball_loss(outputs, labels, self.cfg.quantiles)
         return pinball_loss(outputs, labels, self.cfg.quantiles)
 
     # -------------------------------------------------- long-horizon path

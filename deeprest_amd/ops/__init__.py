@@ -19,7 +19,8 @@ from .layernorm import layer_norm, reference_layer_norm
 from .residual_norm import (dropout_add, dropout_add_layer_norm, philox_keep_mask,
                             reference_dropout_add_layer_norm)
 from .attention import mha_forward, reference_mha
-from .pinball import pinball_loss, reference_pinball_loss
+from .pinball import (masked_pinball_loss, pinball_loss,
+                      reference_masked_pinball_loss, reference_pinball_loss)
 from .adam import fused_adam_step
 
 __all__ = [
@@ -40,5 +41,7 @@ __all__ = [
     "reference_mha",
     "pinball_loss",
     "reference_pinball_loss",
+    "masked_pinball_loss",
+    "reference_masked_pinball_loss",
     "fused_adam_step",
 ]
