@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <string>
 #include <vector>
 
 // ---- C ABI launchers from the .hip translation units ----
@@ -69,9 +70,10 @@ int dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
                const void* h_all, const void* saves, void* dpre, float* dh0,
                int B, int TT, int C, int reverse, int is_bf16,
                hipStream_t stream);
+int dr_gru_reduce_fused_max_c();
 int dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
                       void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
-                      void* xg_pi, int64_t BT, int C, int is_bf16,
+                      void* xg_pi, int64_t BT, int C, int mode, int is_bf16,
                       hipStream_t stream);
 void dr_mha_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                 int64_t BH, int T_len, int D, float scale, int is_bf16,
@@ -634,13 +636,33 @@ std::vector<at::Tensor> gru_seq_backward_heads_kernel(
                            b_hh, h0, h_all, saves, reverse);
 }
 
-// single-pass reductions over dpre: dxg, dgamma, dbeta
+// reductions over dpre (B, T, C, 4H), pi-packed slices dr|dz|d_hhn|dn:
+// dxg (B, T, 3H), dgamma (C, 3H) f32, and dbeta4 (C, 4H) f32 in dpre's slice
+// order (its d_hhn slice is the n-part of db_hh).  mode "fused" reads every
+// dpre row once (C up to gru_reduce_fused_max_c()), "split" is the two-kernel
+// form that reads it twice, "auto" takes the single pass wherever it applies.
 std::vector<at::Tensor> gru_bwd_reduce(at::Tensor dpre, at::Tensor gamma,
-                                       at::Tensor xg) {
+                                       at::Tensor xg, const std::string& mode) {
   const at::cuda::CUDAGuard guard(dpre.device());
+  check_dtype(dpre, "dpre");
   TORCH_CHECK(dpre.dim() == 4 && dpre.size(3) == 512);
   int64_t BT = dpre.size(0) * dpre.size(1);
   int C = (int)dpre.size(2);
+  TORCH_CHECK(BT > 0 && C > 0, "gru_bwd_reduce: empty dpre");
+  TORCH_CHECK(gamma.sizes() == at::IntArrayRef({C, 384}) &&
+                  xg.sizes() == at::IntArrayRef({dpre.size(0), dpre.size(1), 384}),
+              "gru_bwd_reduce: gamma must be (C, 3H) and xg (B, T, 3H)");
+  TORCH_CHECK(gamma.scalar_type() == dpre.scalar_type() &&
+                  xg.scalar_type() == dpre.scalar_type() && gamma.is_cuda() &&
+                  xg.is_cuda(),
+              "gru_bwd_reduce: gamma and xg must match dpre's dtype and device");
+  int mode_id = 0;
+  if (mode == "split") mode_id = 1;
+  else if (mode == "fused") mode_id = 2;
+  else TORCH_CHECK(mode == "auto", "gru_bwd_reduce: mode must be auto, split or fused, got ", mode);
+  TORCH_CHECK(mode_id != 2 || C <= dr_gru_reduce_fused_max_c(),
+              "gru_bwd_reduce: the fused mode covers C <= ",
+              dr_gru_reduce_fused_max_c(), ", got C = ", C);
   TORCH_CHECK(xg.is_contiguous() && gamma.is_contiguous() && dpre.is_contiguous());
   auto dxg = at::empty({dpre.size(0), dpre.size(1), 384}, dpre.options());
   auto dgamma = at::zeros({C, 384}, dpre.options().dtype(at::kFloat));
@@ -652,7 +674,8 @@ std::vector<at::Tensor> gru_bwd_reduce(at::Tensor dpre, at::Tensor gamma,
       dr_gru_bwd_reduce(dpre.data_ptr(), gamma.data_ptr(), xg.data_ptr(),
                         dxg.data_ptr(), dgamma.data_ptr<float>(),
                         dbeta.data_ptr<float>(), gamma_pi.data_ptr(),
-                        xg_pi.data_ptr(), BT, C, is_bf16(dpre), cur_stream()),
+                        xg_pi.data_ptr(), BT, C, mode_id, is_bf16(dpre),
+                        cur_stream()),
       "gru backward reductions");
   return {dxg, dgamma, dbeta};
 }
@@ -731,7 +754,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lengths") = py::none());
   m.def("gru_seq_backward_kernel", &gru_seq_backward_kernel);
   m.def("gru_seq_backward_heads_kernel", &gru_seq_backward_heads_kernel);
-  m.def("gru_bwd_reduce", &gru_bwd_reduce);
+  m.def("gru_bwd_reduce", &gru_bwd_reduce, py::arg("dpre"), py::arg("gamma"),
+        py::arg("xg"), py::arg("mode") = "auto");
+  m.def("gru_reduce_fused_max_c", &dr_gru_reduce_fused_max_c);
   m.def("mha_forward", &mha_forward, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("scale"), py::arg("kv_lengths") = py::none());
   m.def("mha_backward", &mha_backward);

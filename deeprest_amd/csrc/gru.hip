@@ -11,8 +11,8 @@
 // (g = xg * gamma + beta).  State stays fp32; GEMM operands are bf16
 // (SURVEY.md "keep state in fp32, activations in low precision").
 //
-// IO layout note: the training-only side tensors (forward saves r|z|n|hh_n,
-// backward dpre dr|dz|dn|d_hhn) use a within-row permutation "pi":
+// IO layout note: the training-only side tensors (forward saves r|z,
+// backward dpre dr|dz|d_hhn|dn) use a within-row permutation "pi":
 //   pi(gate, col) = gate*H + (col & 15)*8 + (col >> 4)
 // so each lane's 8 values per gate (its MFMA C-fragment columns, stride 16)
 // are CONTIGUOUS 16 bytes -> one vector load/store instead of 8 scalars.
@@ -24,8 +24,9 @@
 // CU writes then reads it after __syncthreads; per-CU L1 is updated by its
 // own stores), against a pi-row-permuted W image in LDS, so no LDS dpre
 // image and one barrier per step.  Batched reductions (dW_hh, db_hh, dgamma,
-// dbeta, dx_gates) happen outside: rocBLAS GEMMs + the fused reduce kernels
-// below (driven by ops/gru.py).
+// dbeta, dx_gates) happen outside: one rocBLAS GEMM over dpre's first three
+// slices (the MFMA K axis below, which is why d_hhn sits before dn) + the
+// reduce kernels below (driven by ops/gru.py).
 //
 // Fixed geometry: H = 128, 3H = 384, 64 rows/block, 4 waves, 256 threads.
 #include "common.h"
@@ -649,8 +650,8 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
 
 // ---------------------------------------------------------------- backward
 // The MFMA K axis runs over pi positions m in [0, 384): regions {dr, dz,
-// d_hhn} of the dpre tensor (skipping the dn region, which only feeds the
-// x-side).  A-fragments read the just-written GLOBAL dpre rows (same-CU L2
+// d_hhn}, the first three slices of a dpre row (dn, which only feeds the
+// x-side, comes last).  A-fragments read the just-written GLOBAL dpre rows (same-CU L2
 // after __syncthreads); the B image in LDS is W^T with rows permuted to the
 // same m ordering, so both sides agree on any K permutation.
 // NSUB = 1: 4 waves / 64 rows, no LDS, W streamed from L2 (2 blocks/CU can
@@ -677,7 +678,7 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
     const T* __restrict__ h0,       // (B, C, H)
     const T* __restrict__ h_all,    // (B, TT, C, H)
     const T* __restrict__ saves,    // (B, TT, C, 2H) pi layout: r|z
-    T* __restrict__ dpre,           // (B, TT, C, 4H) pi: dr|dz|dn|d_hhn
+    T* __restrict__ dpre,           // (B, TT, C, 4H) pi: dr|dz|d_hhn|dn
     float* __restrict__ dh0,        // (B, C, H)
     int B, int TT, int C, int reverse, int O) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -886,8 +887,8 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
       T* dx_p = dpre + bc * G4H + c_col * 8;
       st8(dx_p, fdr);
       st8(dx_p + H, fdz);
-      st8(dx_p + 2 * H, fdn);
-      st8(dx_p + 3 * H, fdh);
+      st8(dx_p + 2 * H, fdh);
+      st8(dx_p + 3 * H, fdn);
       // fence the scheduler: without this it interleaves all 4 row
       // iterations and the combined live ranges spill to scratch
       __builtin_amdgcn_sched_barrier(0);
@@ -909,11 +910,8 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
       const T* arow_p = dpre + (abc0 + bc_toff) * G4H;
       bf16x8 afrag[12];
 #pragma unroll
-      for (int kt = 0; kt < 12; ++kt) {
-        int m = kt * 32 + k0;
-        int off = (m < 256) ? m : (m + 128);   // skip the dn region (g == 2)
-        afrag[kt] = ld_frag(arow_p + off);
-      }
+      for (int kt = 0; kt < 12; ++kt)
+        afrag[kt] = ld_frag(arow_p + kt * 32 + k0);
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) {
         f32x4 a = {0.f, 0.f, 0.f, 0.f};
@@ -952,8 +950,18 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
 
 // ------------------------------------------------- backward reductions
 // One pass over dpre per kernel (replaces the einsum broadcasts that
-// dominated the profiled step).  Both kernels understand the pi layout and
-// emit NATURAL-order outputs.
+// dominated the profiled step).  All kernels understand the pi layout and
+// dpre's slice order dr|dz|d_hhn|dn, and emit NATURAL-order outputs.  The
+// x-side gates (r, z, n) are slices 0, 1, 3; slice 2 (d_hhn) only feeds
+// dbeta4, whose slices follow dpre's order.
+//   C <= REDUCE_FUSED_MAX_C: gru_reduce_fused_kernel reads each row once.
+//   above (or on request):   gru_dxg_kernel + gru_dgamma_kernel, two reads.
+
+// dpre slice of x-side gate g, and the gate a slice feeds (-1: none)
+__device__ __forceinline__ int slice_of_gate(int g) { return g < 2 ? g : 3; }
+__device__ __forceinline__ int gate_of_slice(int s) {
+  return s < 2 ? s : (s == 3 ? 2 : -1);
+}
 
 // natural (r, 3H) -> pi-layout copy: position g*H + cc*8 + e holds natural
 // column g*H + cc + 16e.  Run ONCE per tensor so the reduction kernels'
@@ -996,7 +1004,7 @@ __global__ void gru_dxg_kernel(const T* __restrict__ dpre,     // (BT, C, 4H) pi
     float acc[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    const T* base = dpre + bt * C * G4H + pi0;
+    const T* base = dpre + bt * C * G4H + slice_of_gate(g) * H + cc * 8;
     // 4x unroll: the c loop has a runtime bound, so without it the
     // compiler keeps ONE 1-KB wave read in flight and the kernel is
     // latency-bound at ~2.7 TB/s (measured; 4 concurrent reads ~ 4x MLP)
@@ -1028,7 +1036,7 @@ __global__ void gru_dxg_kernel(const T* __restrict__ dpre,     // (BT, C, 4H) pi
 }
 
 // dgamma[c, j<3H] = sum_bt dpre[bt, c, pi(j)] * xg[bt, j]
-// dbeta4[c, j<4H] = sum_bt dpre[bt, c, pi(j)]   (4th slice -> db_hh_n)
+// dbeta4[c, j<4H] = sum_bt dpre[bt, c, pi(j)]   (slice 2, d_hhn -> db_hh_n)
 // grid.y slices BT; f32 atomics finalize.  Natural-order outputs.
 // xg_pi is the pi-permuted xg image: one ld8 per bt instead of 8 scalars.
 template <typename T>
@@ -1042,10 +1050,12 @@ __global__ void gru_dgamma_kernel(const T* __restrict__ dpre,   // (BT, C, 4H) p
   if (tid_g >= n_threads_needed) return;
   const int c = tid_g / 64;
   const int rem = tid_g % 64;
-  const int g = rem / 16;
+  const int s = rem / 16;                // dpre slice
   const int cc = rem % 16;
-  const bool has_x = g < 3;
-  const int pi0 = g * H + cc * 8;
+  const int g = gate_of_slice(s);
+  const bool has_x = g >= 0;
+  const int pi0 = s * H + cc * 8;        // in the dpre row
+  const int xpi0 = g * H + cc * 8;       // in the xg_pi row (has_x only)
   const int64_t bt_lo = BT * blockIdx.y / gridDim.y;
   const int64_t bt_hi = BT * (blockIdx.y + 1) / gridDim.y;
   float accg[8], accb[8];
@@ -1062,7 +1072,7 @@ __global__ void gru_dgamma_kernel(const T* __restrict__ dpre,   // (BT, C, 4H) p
       float xv[4][8];
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        ld8(xg_pi + (bt + u) * G3H + pi0, xv[u]);
+        ld8(xg_pi + (bt + u) * G3H + xpi0, xv[u]);
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -1078,20 +1088,249 @@ __global__ void gru_dgamma_kernel(const T* __restrict__ dpre,   // (BT, C, 4H) p
     ld8(dpre + (bt * C + c) * G4H + pi0, d);
     if (has_x) {
       float xv[8];
-      ld8(xg_pi + bt * G3H + pi0, xv);
+      ld8(xg_pi + bt * G3H + xpi0, xv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) accg[e] += d[e] * xv[e];
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) accb[e] += d[e];
   }
-  float* b_out = dbeta4 + (int64_t)c * G4H + g * H + cc;
+  float* b_out = dbeta4 + (int64_t)c * G4H + s * H + cc;
 #pragma unroll
   for (int e = 0; e < 8; ++e) atomicAdd(b_out + e * 16, accb[e]);
   if (has_x) {
     float* g_out = dgamma + (int64_t)c * G3H + g * H + cc;
 #pragma unroll
     for (int e = 0; e < 8; ++e) atomicAdd(g_out + e * 16, accg[e]);
+  }
+}
+
+// ---- single pass: dxg, dgamma and dbeta4 from ONE read of each dpre row ----
+// A workgroup of RF_WAVES waves owns a contiguous slab of bt rows and all C
+// components.  One wave reads one whole row (lane = slice x 8-column chunk,
+// 16 B per lane in bf16), and wave w owns components {w, w + RF_WAVES, ...},
+// CPT of them, so its dgamma / dbeta4 partials stay in registers over the
+// slab and leave the block once, as f32 atomics.  For dxg each lane pre-sums
+// its own components times their gamma_pi rows (staged in LDS once per
+// block); the RF_WAVES partial rows meet in a double-buffered LDS area (one
+// barrier per bt, no atomics in the loop) and the first 384 threads store
+// the dxg row contiguously in natural order.  The next bt's rows are in
+// flight while the current one is consumed.
+constexpr int REDUCE_FUSED_MAX_C = 64;   // RF_WAVES x the largest CPT
+constexpr int RF_WAVES = 8;
+constexpr int RF_GSTR = H + 16;          // partial-row gate stride: the two
+                                         // slices of a half-wave hit
+                                         // different LDS banks
+constexpr int RF_PSTR = 3 * RF_GSTR;     // one wave's partial dxg row (f32)
+
+template <typename T, int CPT>
+struct ReduceLds {
+  static constexpr int GAM = 0;          // (RF_WAVES*CPT, 3H) T, pi layout
+  static constexpr int PART = GAM + RF_WAVES * CPT * G3H * (int)sizeof(T);
+  static constexpr int TOTAL = PART + 2 * RF_WAVES * RF_PSTR * 4;
+  static_assert(TOTAL <= LDS_MAX, "reduce LDS layout exceeds a workgroup's LDS");
+};
+
+// 8 values as loaded (bf16: 4 registers), converted only where consumed
+template <typename T> struct Pack8;
+template <> struct Pack8<uint16_t> { uint4 v; };
+template <> struct Pack8<float> { float4 a, b; };
+__device__ __forceinline__ void unpack8(const Pack8<uint16_t>& p, float* v) {
+  const uint32_t w[4] = {p.v.x, p.v.y, p.v.z, p.v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = __uint_as_float(w[i] << 16);
+    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+  }
+}
+__device__ __forceinline__ void unpack8(const Pack8<float>& p, float* v) {
+  v[0] = p.a.x; v[1] = p.a.y; v[2] = p.a.z; v[3] = p.a.w;
+  v[4] = p.b.x; v[5] = p.b.y; v[6] = p.b.z; v[7] = p.b.w;
+}
+
+// raw buffer load of 8 values at a byte offset into a scalar descriptor
+constexpr int BUF_RSRC_W3 = 0x00020000;  // gfx9 raw-buffer word 3: 32-bit data format
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+template <typename T>
+__device__ __forceinline__ Pack8<T> ld_buf8(__amdgpu_buffer_rsrc_t r, uint32_t off);
+template <>
+__device__ __forceinline__ Pack8<uint16_t> ld_buf8<uint16_t>(__amdgpu_buffer_rsrc_t r,
+                                                             uint32_t off) {
+  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+  return {make_uint4(v.x, v.y, v.z, v.w)};
+}
+template <>
+__device__ __forceinline__ Pack8<float> ld_buf8<float>(__amdgpu_buffer_rsrc_t r,
+                                                       uint32_t off) {
+  const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+  const u32x4 b = __builtin_amdgcn_raw_buffer_load_b128(r, off + 16, 0, 0);
+  return {make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z),
+                      __uint_as_float(a.w)),
+          make_float4(__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z),
+                      __uint_as_float(b.w))};
+}
+
+// The 8 values exist in their own registers from here on, and nothing
+// scheduled after this point moves before it: a refill issued next can land
+// in the registers the values were unpacked from (no copy of the ring at the
+// loop's back edge, which would wait for every load in flight).
+__device__ __forceinline__ void take_out(float* v) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(v[e]));
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// LDS-only workgroup barrier: waits for this wave's LDS traffic, not for its
+// global loads, so the prefetched rows stay in flight across it
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+template <typename T, int CPT>
+__global__ __launch_bounds__(RF_WAVES * DR_WAVE) void gru_reduce_fused_kernel(
+    const T* __restrict__ dpre,      // (BT, C, 4H) pi: dr|dz|d_hhn|dn
+    const T* __restrict__ gamma_pi,  // (C, 3H) pi
+    const T* __restrict__ xg_pi,     // (BT, 3H) pi
+    T* __restrict__ dxg,             // (BT, 3H)
+    float* __restrict__ dgamma,      // (C, 3H) zeroed
+    float* __restrict__ dbeta4,      // (C, 4H) zeroed, dpre's slice order
+    int64_t BT, int C) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using L = ReduceLds<T, CPT>;
+  using P = Pack8<T>;
+  constexpr int NTHR = RF_WAVES * DR_WAVE;
+  T* gam = reinterpret_cast<T*>(smem + L::GAM);
+  float* part = reinterpret_cast<float*>(smem + L::PART);
+  const int tid = threadIdx.x;
+  // the wave index as a scalar: row addresses below are scalar base + lane
+  const int w = __builtin_amdgcn_readfirstlane(tid / DR_WAVE);
+  const int lane = tid % DR_WAVE;
+  const int s = lane >> 4;               // dpre slice
+  const int cc = lane & 15;
+  const int g = gate_of_slice(s);
+  const bool has_x = g >= 0;
+  // d_hhn lanes run the x-side arithmetic on gate 0's operands and drop it
+  // (no divergence inside the wave); they only keep dbeta4
+  const int gx = has_x ? g : 0;
+
+  // gamma_pi rows into LDS in 16-byte pieces; rows past C are zero
+  constexpr int ROW16 = G3H * (int)sizeof(T) / 16;
+  for (int id = tid; id < RF_WAVES * CPT * ROW16; id += NTHR) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (id / ROW16 < C) v = reinterpret_cast<const uint4*>(gamma_pi)[id];
+    reinterpret_cast<uint4*>(gam)[id] = v;
+  }
+  __syncthreads();
+
+  const int64_t bt_lo = BT * blockIdx.x / gridDim.x;
+  const int64_t bt_hi = BT * (blockIdx.x + 1) / gridDim.x;
+  float accg[CPT][8], accb[CPT][8];
+#pragma unroll
+  for (int k = 0; k < CPT; ++k)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { accg[k][e] = 0.f; accb[k][e] = 0.f; }
+
+  // Slots past C re-read component C - 1 (a valid row) against a zero gamma
+  // row and are never flushed, and the last bt of the slab is re-read once
+  // instead of ending the prefetch: every lane issues the same loads in
+  // every iteration, so the wait counters stay exact and nothing drains the
+  // rows in flight.
+  uint32_t voff[CPT];                    // byte offset of slot k in a bt
+#pragma unroll
+  for (int k = 0; k < CPT; ++k)
+    voff[k] = (uint32_t)min(w + k * RF_WAVES, C - 1) * (G4H * (uint32_t)sizeof(T)) +
+              lane * 8 * (uint32_t)sizeof(T);
+  const uint32_t xoff = (gx * H + cc * 8) * (uint32_t)sizeof(T);
+  const T* grow = gam + w * G3H + gx * H + cc * 8;
+  float* pw = part + w * RF_PSTR + gx * RF_GSTR + cc;
+  const float* pr = part + (tid >> 7) * RF_GSTR + (tid & (H - 1));   // tid < 3H
+
+  // Buffer loads: a scalar descriptor per bt (base and size of that bt's C
+  // rows) + one 32-bit lane offset per slot.  With plain pointers the loop
+  // optimizer keeps a 64-bit vector address per slot and CPT = 8 spills.
+  auto row_base = [&](int64_t bt) {
+    return __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<T*>(dpre + bt * C * G4H), 0, C * G4H * (int)sizeof(T), BUF_RSRC_W3);
+  };
+  auto ld_row = [&](__amdgpu_buffer_rsrc_t base, int k) { return ld_buf8<T>(base, voff[k]); };
+  auto ld_x = [&](int64_t bt) {
+    return ld_buf8<T>(__builtin_amdgcn_make_buffer_rsrc(
+                          const_cast<T*>(xg_pi + bt * G3H), 0, G3H * (int)sizeof(T),
+                          BUF_RSRC_W3),
+                      xoff);
+  };
+
+  // A ring of CPT rows (+ the xg row): each register set is refilled with
+  // the next bt's row as soon as this bt's row has been taken out of it, so
+  // one bt of rows per wave is in flight at any time.
+  P ring[CPT], xring;
+  if (bt_lo < bt_hi) {
+    // same issue order as in the loop: the wait counts at its head then hold
+    // for the first iteration and for the back edge alike
+    xring = ld_x(bt_lo);
+    const auto base = row_base(bt_lo);
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) ring[k] = ld_row(base, k);
+  }
+  int boff = 0;                          // partial buffer of this bt
+  for (int64_t bt = bt_lo; bt < bt_hi; ++bt) {
+    const int64_t bt_n = bt + 1 < bt_hi ? bt + 1 : bt;
+    const auto base_n = row_base(bt_n);
+    float xv[8], px[8];
+    unpack8(xring, xv);
+    take_out(xv);
+    xring = ld_x(bt_n);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) px[e] = 0.f;
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+      float d[8], gm[8];
+      unpack8(ring[k], d);
+      take_out(d);
+      ring[k] = ld_row(base_n, k);
+      unpack8(*reinterpret_cast<const P*>(grow + k * RF_WAVES * G3H), gm);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        accb[k][e] += d[e];
+        accg[k][e] += d[e] * xv[e];
+        px[e] += d[e] * gm[e];
+      }
+      // pin this slot's sums here: left alone the optimizer unpacks every
+      // slot first and sinks all the arithmetic below the last refill, and
+      // the CPT x 8 live values spill to scratch
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        asm volatile("" : "+v"(accb[k][e]), "+v"(accg[k][e]), "+v"(px[e]));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (has_x) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) pw[boff + e * 16] = px[e];   // natural column cc + 16e
+    }
+    // this buffer is rewritten two bt later, behind the NEXT barrier, which
+    // every reader of it has passed by then
+    lds_barrier();
+    if (tid < G3H) {
+      float sum = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < RF_WAVES; ++ww) sum += pr[boff + ww * RF_PSTR];
+      stf(dxg + bt * G3H + tid, sum);
+    }
+    boff ^= RF_WAVES * RF_PSTR;
+  }
+
+#pragma unroll
+  for (int k = 0; k < CPT; ++k) {
+    const int c = w + k * RF_WAVES;
+    if (c >= C) continue;
+    float* b_out = dbeta4 + (int64_t)c * G4H + s * H + cc;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) atomicAdd(b_out + e * 16, accb[k][e]);
+    if (has_x) {
+      float* g_out = dgamma + (int64_t)c * G3H + g * H + cc;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) atomicAdd(g_out + e * 16, accg[k][e]);
+    }
   }
 }
 
@@ -1194,11 +1433,45 @@ static hipError_t gru_bwd_launch(const BwdArgs& a) {
   return hipGetLastError();
 }
 
+// compute units of the current device, asked once per process (see allow_lds)
+static int cu_count() {
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      n <= 0)
+    n = 256;
+  return n;
+}
+
+template <typename T, int CPT>
+static hipError_t gru_reduce_fused_launch(const T* dpre, const T* gamma_pi,
+                                          const T* xg_pi, T* dxg, float* dgamma,
+                                          float* dbeta, int64_t BT, int C,
+                                          hipStream_t stream) {
+  constexpr int LDS = ReduceLds<T, CPT>::TOTAL;
+  static const hipError_t attr = allow_lds(&gru_reduce_fused_kernel<T, CPT>, LDS);
+  if (attr != hipSuccess) return attr;
+  // one resident block per CU, each flushing its dgamma / dbeta4 partials once
+  static const int n_cu = cu_count();
+  const int grid = (int)std::min<int64_t>(BT, n_cu);
+  hipLaunchKernelGGL((gru_reduce_fused_kernel<T, CPT>), dim3(grid),
+                     dim3(RF_WAVES * DR_WAVE), LDS, stream, dpre, gamma_pi, xg_pi,
+                     dxg, dgamma, dbeta, BT, C);
+  return hipGetLastError();
+}
+
+enum ReduceMode { REDUCE_AUTO = 0, REDUCE_SPLIT = 1, REDUCE_FUSED = 2 };
+
 template <typename T>
 static hipError_t gru_reduce_launch(const void* dpre, const void* gamma,
                                     const void* xg, void* dxg, float* dgamma,
                                     float* dbeta, void* gamma_pi, void* xg_pi,
-                                    int64_t BT, int C, hipStream_t stream) {
+                                    int64_t BT, int C, int mode,
+                                    hipStream_t stream) {
+  if (BT <= 0 || C <= 0) return hipErrorInvalidValue;
+  if (mode == REDUCE_FUSED && C > REDUCE_FUSED_MAX_C) return hipErrorInvalidValue;
+  const bool fused = mode == REDUCE_FUSED ||
+                     (mode == REDUCE_AUTO && C <= REDUCE_FUSED_MAX_C);
   auto chunk_grid = [](int64_t rows) {
     return (int)std::min<int64_t>((rows * 48 + 255) / 256, 4096);
   };
@@ -1210,6 +1483,18 @@ static hipError_t gru_reduce_launch(const void* dpre, const void* gamma,
   hipLaunchKernelGGL((pi_permute_rows_kernel<T>), dim3(chunk_grid(BT)), dim3(256),
                      0, stream, (const T*)xg, (T*)xg_pi, BT);
   if (hipError_t e = hipGetLastError()) return e;
+  if (fused) {
+    auto run = [&](auto cpt) {
+      return gru_reduce_fused_launch<T, decltype(cpt)::value>(
+          (const T*)dpre, (const T*)gamma_pi, (const T*)xg_pi, (T*)dxg, dgamma,
+          dbeta, BT, C, stream);
+    };
+    const int need = (C + RF_WAVES - 1) / RF_WAVES;   // components per wave
+    if (need <= 1) return run(std::integral_constant<int, 1>{});
+    if (need <= 2) return run(std::integral_constant<int, 2>{});
+    if (need <= 4) return run(std::integral_constant<int, 4>{});
+    return run(std::integral_constant<int, 8>{});
+  }
   hipLaunchKernelGGL((gru_dxg_kernel<T>), dim3(chunk_grid(BT)), dim3(256), 0,
                      stream, (const T*)dpre, (const T*)gamma_pi, (T*)dxg, BT, C);
   if (hipError_t e = hipGetLastError()) return e;
@@ -1293,15 +1578,20 @@ int dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
   return (int)(fused ? run(std::true_type{}) : run(std::false_type{}));
 }
 
+// largest C the single-pass reduce kernel covers
+int dr_gru_reduce_fused_max_c() { return dr::REDUCE_FUSED_MAX_C; }
+
+// mode: 0 auto (single pass up to its C limit, the two-kernel form above it),
+// 1 the two-kernel form, 2 the single pass (an error above its limit).
 // returns the first failing launch's error
 int dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
                       void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
-                      void* xg_pi, int64_t BT, int C, int is_bf16,
+                      void* xg_pi, int64_t BT, int C, int mode, int is_bf16,
                       hipStream_t stream) {
   return (int)dr::with_io_type(is_bf16, [&](auto io) {
     using T = typename decltype(io)::type;
     return dr::gru_reduce_launch<T>(dpre, gamma, xg, dxg, dgamma, dbeta,
-                                    gamma_pi, xg_pi, BT, C, stream);
+                                    gamma_pi, xg_pi, BT, C, mode, stream);
   });
 }
 

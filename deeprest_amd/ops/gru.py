@@ -132,7 +132,7 @@ class _FusedGRUSequence(torch.autograd.Function):
         x_gates, w_hh, b_hh, h0, gamma, beta, h_all, saves = ctx.saved_tensors
         reverse = ctx.reverse
         w_img, w_fwd = _bwd_weight_images(w_hh)
-        # sequential chain (custom kernel): dpre = [dr_pre|dz_pre|dn_pre|d_hh_n]
+        # sequential chain (custom kernel): dpre = [dr_pre|dz_pre|d_hh_n|dn_pre]
         dpre, dh0 = ext.gru_seq_backward_kernel(
             grad_h_all.contiguous(), w_img, w_fwd, x_gates, gamma, beta, b_hh,
             h0, h_all, saves, reverse
@@ -153,6 +153,30 @@ def _bwd_weight_images(w_hh):
     return w_img, w_fwd
 
 
+# Which reduce kernels _bwd_reductions asks for: "auto" (the single pass
+# wherever it applies), "split" or "fused".  Tests and tools/bench_gru_reduce.py
+# set it to pin one path.
+REDUCE_MODE = "auto"
+
+
+def reference_bwd_reduce(dpre, gamma, xg):
+    """What ext.gru_bwd_reduce computes, in plain torch and in the inputs'
+    dtype (pass float64 for a reference): dpre (B, T, C, 4H) holds the
+    pi-packed slices dr|dz|d_hhn|dn.  Returns, in the binding's layout,
+    dxg (B, T, 3H), dgamma (C, 3H) and dbeta4 (C, 4H): columns in natural
+    order, dbeta4's slices in dpre's order."""
+    B, T, C, G4 = dpre.shape
+    H = G4 // 4
+    _, nat4 = _pi_indices(dpre.device)
+    nat = torch.empty_like(dpre)
+    nat.index_copy_(3, nat4, dpre)                      # unpermute each slice
+    dx = torch.cat([nat[..., : 2 * H], nat[..., 3 * H:]], dim=-1)  # r|z|n
+    dxg = (dx * gamma).sum(dim=2)
+    dgamma = (dx * xg[:, :, None, :]).sum(dim=(0, 1))
+    dbeta4 = nat.sum(dim=(0, 1))
+    return dxg, dgamma, dbeta4
+
+
 def _bwd_reductions(ext, dpre, dh0, x_gates, w_hh, h0, gamma, h_all, reverse):
     """Everything after the sequential chain, shared by the plain and the
     head-fused backward: returns (dxg, dw_hh, db_hh, dh0, dgamma, dbeta)."""
@@ -164,40 +188,32 @@ def _bwd_reductions(ext, dpre, dh0, x_gates, w_hh, h0, gamma, h_all, reverse):
     # the GEMM (tiny index_copy on a (K, H) matrix).
     _, nat4 = _pi_indices(w_hh.device)
 
-    def unpi(dw_pi):
-        out = torch.empty_like(dw_pi)
-        out.index_copy_(0, nat4[: dw_pi.shape[0]], dw_pi)
-        return out
+    # dW_hh = sum over (b,t,c) of [dr|dz|d_hhn]^T h_prev: dpre's first three
+    # slices, so ONE batched strided GEMM (rocBLAS picks per-B batching =>
+    # proper chip occupancy; no cats: the t=0/t=T-1 boundary term against h0
+    # is a separate small bmm; at T = 1 the main part is empty and adds zero)
+    if reverse:
+        dp_main = dpre[:, :-1, :, : 3 * H]              # h_prev = h_all[t+1]
+        h_main = h_all[:, 1:]
+        dp_bound = dpre[:, -1, :, : 3 * H]              # h_prev = h0
+    else:
+        dp_main = dpre[:, 1:, :, : 3 * H]               # h_prev = h_all[t-1]
+        h_main = h_all[:, :-1]
+        dp_bound = dpre[:, 0, :, : 3 * H]
+    a = dp_main.reshape(B, (T - 1) * C, 3 * H).transpose(1, 2)
+    part = torch.bmm(a, h_main.reshape(B, (T - 1) * C, H))
+    ab = dp_bound.reshape(B, C, 3 * H).transpose(1, 2)
+    part = part + torch.bmm(ab, h0)
+    dw_pi = part.sum(0, dtype=torch.float32)            # (3H, H), pi rows
+    dw_hh = torch.empty_like(dw_pi)
+    dw_hh.index_copy_(0, nat4[: 3 * H], dw_pi)          # natural rows r|z|n
 
-    # dW_hh = sum over (b,t,c) of [dr|dz|d_hhn]^T h_prev — batched strided
-    # GEMMs (rocBLAS picks per-B batching => proper chip occupancy; no cats:
-    # the t=0/t=T-1 boundary term against h0 is a separate small bmm)
-    def dw_for(cols):
-        if reverse:
-            dp_main = dpre[:, :-1, :, cols]             # h_prev = h_all[t+1]
-            h_main = h_all[:, 1:]
-            dp_bound = dpre[:, -1, :, cols]             # h_prev = h0
-        else:
-            dp_main = dpre[:, 1:, :, cols]              # h_prev = h_all[t-1]
-            h_main = h_all[:, :-1]
-            dp_bound = dpre[:, 0, :, cols]
-        K = dp_main.shape[-1]
-        a = dp_main.reshape(B, (T - 1) * C, K).transpose(1, 2)
-        part = torch.bmm(a, h_main.reshape(B, (T - 1) * C, H))
-        ab = dp_bound.reshape(B, C, K).transpose(1, 2)
-        part = part + torch.bmm(ab, h0)
-        return unpi(part.sum(0, dtype=torch.float32))   # (K, H) natural rows
-
-    dw_rz = dw_for(slice(0, 2 * H))
-    dw_n = dw_for(slice(3 * H, 4 * H))
-    dw_hh = torch.cat([dw_rz, dw_n], dim=0)             # (3H, H) f32
-
-    # single-pass fused reductions (custom kernel): dxg, dgamma, dbeta4
-    # (dbeta4's 4th slice is sum of d_hh_n -> the n-part of db_hh)
-    dxg, dgamma, dbeta4 = ext.gru_bwd_reduce(dpre, gamma, x_gates)
-    s4 = dbeta4.sum(dim=0)                              # (4H,) f32, tiny
-    db_hh = torch.cat([s4[: 2 * H], s4[3 * H :]])
-    dbeta = dbeta4[:, : 3 * H]
+    # reductions over dpre (custom kernels): dxg, dgamma, dbeta4.  dbeta4
+    # follows dpre's slice order r|z|hh_n|n: the first three slices summed
+    # over C are db_hh, slices r, z, n are dbeta.
+    dxg, dgamma, dbeta4 = ext.gru_bwd_reduce(dpre, gamma, x_gates, REDUCE_MODE)
+    db_hh = dbeta4[:, : 3 * H].sum(dim=0)               # (3H,) f32, tiny
+    dbeta = torch.cat([dbeta4[:, : 2 * H], dbeta4[:, 3 * H:]], dim=1)
     return (
         dxg,
         dw_hh.to(w_hh.dtype),
