@@ -82,6 +82,13 @@ void dr_mha_bwd(const void* q, const void* k, const void* v, const void* o,
                 const void* dout, const float* lse, float* dq, void* dk, void* dv,
                 int64_t BH, int T_len, int D, float scale, int is_bf16,
                 hipStream_t stream);
+int dr_sanity_scores(const void* out, const float* measured, const float* base,
+                     const float* y_min, const float* y_scale,
+                     const float* conformal, const int* lengths, int64_t N,
+                     int TT, int M, int log1p, float threshold, int min_run,
+                     float* scores, uint8_t* flags, float* max_score,
+                     int* n_flagged, int* first_flag, int* n_observed,
+                     float* bands, int is_bf16, hipStream_t stream);
 }
 
 namespace {
@@ -725,6 +732,81 @@ std::vector<at::Tensor> mha_backward(at::Tensor q, at::Tensor k, at::Tensor v,
   return {dq, dk, dv};
 }
 
+// ----------------------------------------------------------------- sanity
+// Normalized model output (N, T, M, 3) + measured utilization (N, T, M) ->
+// {scores (N,T,M) f32, flags (N,T,M) u8, max_score, n_flagged, first_flag,
+// n_observed (N,M), bands (N,T,M,3) f32 or empty}; semantics in sanity.hip.
+// Every operand is checked here: bad input is an exception, never a launch.
+// The VALUES of lengths are not read on the host (the kernel clamps them).
+std::vector<at::Tensor> band_scores(at::Tensor out, at::Tensor measured,
+                                    at::Tensor y_min, at::Tensor y_scale,
+                                    c10::optional<at::Tensor> base,
+                                    c10::optional<at::Tensor> conformal,
+                                    bool log1p,
+                                    c10::optional<at::Tensor> lengths,
+                                    double threshold, int64_t min_run,
+                                    bool want_bands) {
+  const at::cuda::CUDAGuard guard(out.device());
+  check_dtype(out, "band_scores out");
+  TORCH_CHECK(out.is_cuda() && out.dim() == 4 && out.is_contiguous(),
+              "band_scores out must be a contiguous (N, T, M, 3) GPU tensor");
+  TORCH_CHECK(out.size(3) == 3, "band_scores is defined on the quantile triple: "
+              "out must have Q = 3, got ", out.size(3));
+  TORCH_CHECK(min_run >= 1 && min_run < (1LL << 31),
+              "band_scores min_run must be >= 1, got ", min_run);
+  const int64_t N = out.size(0), T = out.size(1), M = out.size(2);
+  TORCH_CHECK(T < (1LL << 31) && M < (1LL << 31) && N * M < (1LL << 31) * 64,
+              "band_scores shape too large");
+  auto f32_on_dev = [&](const at::Tensor& t, at::IntArrayRef shape,
+                        const char* name) {
+    TORCH_CHECK(t.scalar_type() == at::kFloat && t.device() == out.device() &&
+                    t.is_contiguous() && t.sizes() == shape,
+                "band_scores ", name, " must be a contiguous f32 tensor of shape ",
+                shape, " on out's device");
+  };
+  f32_on_dev(measured, {N, T, M}, "measured");
+  f32_on_dev(y_min, {M}, "y_min");
+  f32_on_dev(y_scale, {M}, "y_scale");
+  if (base.has_value()) f32_on_dev(*base, {N, T, M}, "base");
+  if (conformal.has_value()) f32_on_dev(*conformal, {M}, "conformal");
+  if (lengths.has_value())
+    TORCH_CHECK(lengths->dim() == 1, "band_scores lengths must be (N,)");
+  const int* lens = lengths_ptr(lengths, out, N, "band_scores lengths");
+  auto f32 = out.options().dtype(at::kFloat);
+  auto i32 = out.options().dtype(at::kInt);
+  auto scores = at::empty({N, T, M}, f32);
+  auto flags = at::empty({N, T, M}, out.options().dtype(at::kByte));
+  auto max_score = at::empty({N, M}, f32);
+  auto n_flagged = at::empty({N, M}, i32);
+  auto first_flag = at::empty({N, M}, i32);
+  auto n_observed = at::empty({N, M}, i32);
+  auto bands = want_bands ? at::empty({N, T, M, 3}, f32) : at::empty({0}, f32);
+  if (N * M == 0) return {scores, flags, max_score, n_flagged, first_flag,
+                          n_observed, bands};
+  if (T == 0) {                       // nothing to loop over: empty summaries
+    max_score.zero_();
+    n_flagged.zero_();
+    first_flag.fill_(-1);
+    n_observed.zero_();
+    return {scores, flags, max_score, n_flagged, first_flag, n_observed, bands};
+  }
+  gru_launch_check(
+      dr_sanity_scores(out.data_ptr(), measured.data_ptr<float>(),
+                       base.has_value() ? base->data_ptr<float>() : nullptr,
+                       y_min.data_ptr<float>(), y_scale.data_ptr<float>(),
+                       conformal.has_value() ? conformal->data_ptr<float>()
+                                             : nullptr,
+                       lens, N, (int)T, (int)M, log1p ? 1 : 0, (float)threshold,
+                       (int)min_run, scores.data_ptr<float>(),
+                       flags.data_ptr<uint8_t>(), max_score.data_ptr<float>(),
+                       n_flagged.data_ptr<int>(), first_flag.data_ptr<int>(),
+                       n_observed.data_ptr<int>(),
+                       want_bands ? bands.data_ptr<float>() : nullptr,
+                       is_bf16(out), cur_stream()),
+      "band_scores");
+  return {scores, flags, max_score, n_flagged, first_flag, n_observed, bands};
+}
+
 }  // namespace
 
 void register_featurize(py::module_& m);
@@ -760,4 +842,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mha_forward", &mha_forward, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("scale"), py::arg("kv_lengths") = py::none());
   m.def("mha_backward", &mha_backward);
+  m.def("band_scores", &band_scores, py::arg("out"), py::arg("measured"),
+        py::arg("y_min"), py::arg("y_scale"), py::arg("base") = py::none(),
+        py::arg("conformal") = py::none(), py::arg("log1p") = false,
+        py::arg("lengths") = py::none(), py::arg("threshold") = 0.25,
+        py::arg("min_run") = 3, py::arg("want_bands") = false);
 }

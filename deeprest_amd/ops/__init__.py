@@ -22,6 +22,7 @@ from .attention import mha_forward, reference_mha
 from .pinball import (masked_pinball_loss, pinball_loss,
                       reference_masked_pinball_loss, reference_pinball_loss)
 from .adam import fused_adam_step
+from .sanity import BandScores, band_scores, reference_band_scores
 
 __all__ = [
     "native_available",
@@ -44,4 +45,7 @@ __all__ = [
     "masked_pinball_loss",
     "reference_masked_pinball_loss",
     "fused_adam_step",
+    "BandScores",
+    "band_scores",
+    "reference_band_scores",
 ]

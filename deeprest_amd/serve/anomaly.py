@@ -27,6 +27,16 @@ class AnomalyReport:
         return bool(self.flags.any())
 
 
+def flag_intervals(flags: np.ndarray) -> List[tuple]:
+    """Contiguous flagged intervals [(start, end), ...], end exclusive — the
+    ``windows`` of an AnomalyReport, for flags computed elsewhere (the device
+    sanity check, ``Predictor.sanity_check``)."""
+    f = np.asarray(flags).astype(bool)
+    edges = np.diff(np.concatenate(([False], f, [False])).astype(np.int8))
+    return [(int(s), int(e)) for s, e in zip(np.flatnonzero(edges == 1),
+                                             np.flatnonzero(edges == -1))]
+
+
 class AnomalyScorer:
     def __init__(self, threshold: float = 0.25, min_run: int = 3) -> None:
         """threshold: relative exceedance over the q95 band that counts;

@@ -15,7 +15,11 @@ Endpoints (FastAPI; run with `uvicorn deeprest_amd.serve.api:create_app`):
                                   concurrent requests coalesce into one
                                   hipGraph replay (serve/batcher.py)
 - POST /anomaly                   sanity-check measured series against the
-                                  model's quantile band
+                                  model's quantile band: post {'windows',
+                                  'measured'} and the loaded model's band is
+                                  computed and scored on the device, or post
+                                  {'measured', 'predicted'} to score against
+                                  predictions the client already holds
 - GET  /apis                      known API endpoints (for what-if queries)
 - GET  /results[/{exp}[/{comp}/{metric}]]  browse a results.pkl store (the
                                   reference web-demo's DataLoader surface,
@@ -265,7 +269,57 @@ def create_app(checkpoint_path: Optional[str] = None, predictor: Optional[Predic
 
     @app.post("/anomaly")
     def anomaly(payload: Dict[str, Any]):
-        """payload: {'measured': {metric: [..]}, 'predicted': {metric: [[q05,q50,q95],..]}}"""
+        """Two payloads.
+
+        ``{'windows': (N, T, P) raw call-path counts, 'measured': ...}`` (no
+        ``'predicted'``): the loaded model's own band is the yardstick
+        (``Predictor.sanity_check``; scores and flags are computed on the
+        device).  ``measured`` is ``{metric: (N, T)}`` — a metric left out is
+        unobserved — or an (N, T, M) list in the model's metric order; JSON
+        ``null`` means "not observed".  Optional ``threshold``, ``min_run``
+        and ``lengths`` ((N,) window lengths, for a server with
+        ``max_window``).  Answers 400 without a loaded model.  Per metric:
+        ``anomalous``, ``windows``, ``max_score``, ``n_observed``; one such
+        dict for a single window, a list of them (one per window) otherwise.
+
+        ``{'measured': {metric: [..]}, 'predicted': {metric:
+        [[q05,q50,q95],..]}}``: the client brings the predictions; scored on
+        the host by ``AnomalyScorer``."""
+        if "predicted" not in payload and "windows" in payload:
+            pred: Optional[Predictor] = state["predictor"]
+            if pred is None:
+                raise HTTPException(status_code=400, detail="no model loaded")
+            if "measured" not in payload:
+                raise HTTPException(status_code=422, detail="measured required")
+            w = np.asarray(payload["windows"], dtype=np.float64)
+            if w.ndim != 3 or w.shape[-1] != pred.model.spec.num_paths:
+                raise HTTPException(
+                    status_code=422,
+                    detail=f"windows must be (N, T, {pred.model.spec.num_paths})")
+            measured = payload["measured"]
+            try:
+                # None (JSON null) becomes NaN: not observed
+                if isinstance(measured, dict):
+                    measured = {k: np.asarray(v, dtype=np.float64)
+                                for k, v in measured.items()}
+                else:
+                    measured = np.asarray(measured, dtype=np.float64)
+                check = pred.sanity_check(
+                    w, measured,
+                    threshold=float(payload.get("threshold", 0.25)),
+                    min_run=int(payload.get("min_run", 3)),
+                    lengths=payload.get("lengths"), detail=True)
+            except (ValueError, TypeError) as e:
+                raise HTTPException(status_code=422, detail=str(e))
+            per_window = []
+            for i in range(w.shape[0]):
+                per_window.append({
+                    k: {"anomalous": r.is_anomalous,
+                        "windows": r.windows,
+                        "max_score": float(check.max_score[i, m]),
+                        "n_observed": int(check.n_observed[i, m])}
+                    for m, (k, r) in enumerate(check.reports(i).items())})
+            return per_window[0] if len(per_window) == 1 else per_window
         scorer = AnomalyScorer(
             threshold=float(payload.get("threshold", 0.25)),
             min_run=int(payload.get("min_run", 3)),

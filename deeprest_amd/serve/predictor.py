@@ -27,10 +27,13 @@ Padded positions come back as NaN.  Measured in profiles/r06_varlen.md.
 
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from .anomaly import AnomalyReport, flag_intervals
 
 from ..data.featurize import FeatureSpace
 from ..data.windows import MinMaxScaler
@@ -38,6 +41,60 @@ from ..engine.checkpoint import load_checkpoint
 from ..models.net import DeepRestNet
 
 DEFAULT_GRAPH_BATCHES = (16, 256, 1024)
+
+
+@dataclass
+class SanityCheck:
+    """What ``Predictor.sanity_check`` found, per window n and metric m.  The
+    (N, M) summaries are host arrays; ``check[metric]`` gives one metric's
+    ``(N,)`` columns.  ``scores`` / ``flags`` (N, T, M) and ``bands``
+    (N, T, M, 3) are device tensors, present with ``detail=True`` only."""
+
+    metric_names: List[str]
+    threshold: float
+    min_run: int
+    max_score: np.ndarray             # (N, M) f32, over observed samples
+    n_flagged: np.ndarray             # (N, M) int32
+    first_flag: np.ndarray            # (N, M) int32, -1: nothing flagged
+    n_observed: np.ndarray            # (N, M) int32
+    scores: Optional[torch.Tensor] = None
+    flags: Optional[torch.Tensor] = None
+    bands: Optional[torch.Tensor] = None
+    lengths: Optional[torch.Tensor] = None    # (N,) int32 as given, or None
+
+    @property
+    def anomalous(self) -> np.ndarray:
+        """(N, M) bool: anything flagged."""
+        return self.n_flagged > 0
+
+    def keys(self) -> List[str]:
+        return list(self.metric_names)
+
+    def __getitem__(self, metric: str) -> Dict[str, np.ndarray]:
+        m = self.metric_names.index(metric)
+        return {"anomalous": self.n_flagged[:, m] > 0,
+                "max_score": self.max_score[:, m],
+                "n_flagged": self.n_flagged[:, m],
+                "first_flag": self.first_flag[:, m],
+                "n_observed": self.n_observed[:, m]}
+
+    def items(self):
+        return [(name, self[name]) for name in self.metric_names]
+
+    def reports(self, i: int) -> Dict[str, AnomalyReport]:
+        """Window i as ``AnomalyScorer.score_all`` would report it (its own
+        length with ``lengths``); the interval lists are built here, on the
+        host, from the flags."""
+        if self.flags is None:
+            raise ValueError("reports() needs sanity_check(..., detail=True)")
+        T = self.flags.shape[1]
+        L = T if self.lengths is None else min(max(int(self.lengths[i]), 1), T)
+        scores = self.scores[i, :L].cpu().numpy()
+        flags = self.flags[i, :L].cpu().numpy().astype(bool)
+        return {name: AnomalyReport(metric=name, scores=scores[:, m],
+                                    flags=flags[:, m],
+                                    windows=flag_intervals(flags[:, m]))
+                for m, name in enumerate(self.metric_names)}
 
 
 class Predictor:
@@ -69,6 +126,7 @@ class Predictor:
                           if conformal is not None else None)
         self._ridge_t: Optional[torch.Tensor] = None    # device caches
         self._conformal_t: Optional[torch.Tensor] = None
+        self._scaler_t: Optional[torch.Tensor] = None
         self.device = device or torch.device(
             "cuda" if torch.cuda.is_available() else "cpu"
         )
@@ -245,6 +303,16 @@ class Predictor:
                                  dtype=np.float32)
         return self.predict_tensor(torch.from_numpy(x).to(self.device))
 
+    def _ridge_base(self, xt: torch.Tensor, device: torch.device) -> torch.Tensor:
+        """The ridge residual base (N, T, M) of normalized traffic xt
+        (N, T, P): one GEMM against the cached device copy of the ridge."""
+        if self._ridge_t is None or self._ridge_t.device != device:
+            self._ridge_t = torch.from_numpy(np.asarray(
+                self.residual_ridge, dtype=np.float32)).to(device)
+        N, T, P = xt.shape
+        base = xt.reshape(-1, P) @ self._ridge_t[:P] + self._ridge_t[P]
+        return base.reshape(N, T, -1)
+
     @torch.no_grad()
     def predict_tensor(self, xt: torch.Tensor,
                        lengths: Optional[torch.Tensor] = None
@@ -263,13 +331,7 @@ class Predictor:
             xt = (xt - self.x_scaler.min_val) * (1.0 / self.x_scaler.scale)
         out = self.predict_normalized(xt, lengths).float()
         if self.residual_ridge is not None:
-            if (self._ridge_t is None
-                    or self._ridge_t.device != out.device):
-                self._ridge_t = torch.from_numpy(np.asarray(
-                    self.residual_ridge, dtype=np.float32)).to(out.device)
-            N, T, P = xt.shape
-            base = xt.reshape(-1, P) @ self._ridge_t[:P] + self._ridge_t[P]
-            out = out + base.reshape(N, T, -1).unsqueeze(-1)
+            out = out + self._ridge_base(xt, out.device).unsqueeze(-1)
         # quantile regression can emit crossed quantiles (q95 < q50) early in
         # training; serving consumers (anomaly bands, demo plots) assume a
         # monotone triple, so sort the Q axis — a no-op once calibrated
@@ -328,6 +390,107 @@ class Predictor:
             torch.tensor(lens, dtype=torch.int32, device=self.device))
         return [{k: v[i, : lens[i]] for k, v in out.items()}
                 for i in range(len(arrs))]
+
+    # ----------------------------------------------------------- sanity check
+    def _scaler_vectors(self, device: torch.device) -> torch.Tensor:
+        """(2, M) f32 on the device: row 0 the per-metric scale, row 1 the
+        min.  A scaler whose scale is 0 leaves its metric alone
+        (``MinMaxScaler.inverse_transform``): scale 1, min 0."""
+        if self._scaler_t is None or self._scaler_t.device != device:
+            live = [s.scale != 0.0 for s in self.y_scalers]
+            v = np.array([[s.scale if ok else 1.0 for s, ok in zip(self.y_scalers, live)],
+                          [s.min_val if ok else 0.0 for s, ok in zip(self.y_scalers, live)]],
+                         dtype=np.float32)
+            self._scaler_t = torch.from_numpy(v).to(device)
+        return self._scaler_t
+
+    def _measured_tensor(self, measured, N: int, T: int) -> torch.Tensor:
+        M = len(self.metric_names)
+        if isinstance(measured, dict):
+            unknown = sorted(set(measured) - set(self.metric_names))
+            if unknown:
+                raise ValueError(f"measured names unknown metrics: {unknown}")
+            arr = np.full((N, T, M), np.nan, dtype=np.float32)
+            for m, name in enumerate(self.metric_names):
+                if name in measured:
+                    a = np.asarray(measured[name], dtype=np.float32)
+                    if a.shape != (N, T):
+                        raise ValueError(
+                            f"measured[{name!r}] must be {(N, T)}, got {a.shape}")
+                    arr[:, :, m] = a
+            return torch.from_numpy(arr).to(self.device)
+        if isinstance(measured, torch.Tensor):
+            y = measured.to(device=self.device, dtype=torch.float32)
+        else:
+            y = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(measured), dtype=np.float32)).to(self.device)
+        if tuple(y.shape) != (N, T, M):
+            raise ValueError(
+                f"measured must be {(N, T, M)} in metric_names order, "
+                f"got {tuple(y.shape)}")
+        return y.contiguous()
+
+    @torch.no_grad()
+    def sanity_check(self, traffic_windows, measured, threshold: float = 0.25,
+                     min_run: int = 3, lengths=None,
+                     detail: bool = False) -> "SanityCheck":
+        """Is the measured utilization justified by the traffic?  Raw count
+        windows (N, T, P) and ``measured`` — an (N, T, M) array in
+        ``metric_names`` order or ``{metric: (N, T)}``, a metric left out being
+        entirely unobserved, a non-finite value "not observed" — are scored
+        against the model's own band without the band leaving the device: the
+        pipeline of ``predict_tensor`` up to the normalized output (graph
+        replay, ``lengths`` / ``max_window`` as there, the ridge GEMM), then
+        ``ops.band_scores``.  Only the (N, M) summaries are copied to the
+        host; with ``detail`` the result also holds scores, flags and bands
+        (device tensors) and ``reports(i)``."""
+        from ..ops.sanity import band_scores
+
+        if int(min_run) < 1:
+            raise ValueError(f"min_run must be >= 1, got {min_run}")
+        if isinstance(traffic_windows, torch.Tensor):
+            xt = traffic_windows.to(device=self.device, dtype=torch.float32)
+        else:
+            xt = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(traffic_windows), dtype=np.float32)).to(self.device)
+        if xt.dim() != 3:
+            raise ValueError(f"traffic windows must be (N, T, P), got {tuple(xt.shape)}")
+        N, T, _ = xt.shape
+        y = self._measured_tensor(measured, N, T)
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(
+                device=self.device, dtype=torch.int32).reshape(-1)
+        if self.x_scaler.scale != 0.0:
+            xt = (xt - self.x_scaler.min_val) * (1.0 / self.x_scaler.scale)
+        out = self.predict_normalized(xt, lengths)
+        if out.dtype not in (torch.float32, torch.bfloat16):
+            out = out.float()
+        base = (self._ridge_base(xt, out.device)
+                if self.residual_ridge is not None else None)
+        conf = None
+        if self.conformal is not None:
+            if (self._conformal_t is None
+                    or self._conformal_t.device != out.device):
+                self._conformal_t = torch.from_numpy(np.asarray(
+                    self.conformal, dtype=np.float32)).to(out.device)
+            conf = self._conformal_t
+        sv = self._scaler_vectors(out.device)
+        res = band_scores(out.contiguous(), y, sv[1], sv[0], base=base,
+                          conformal=conf,
+                          log1p=self.target_transform == "log1p",
+                          lengths=lengths, threshold=float(threshold),
+                          min_run=int(min_run), want_bands=detail)
+        check = SanityCheck(
+            metric_names=list(self.metric_names), threshold=float(threshold),
+            min_run=int(min_run),
+            max_score=res.max_score.cpu().numpy(),
+            n_flagged=res.n_flagged.cpu().numpy(),
+            first_flag=res.first_flag.cpu().numpy(),
+            n_observed=res.n_observed.cpu().numpy())
+        if detail:
+            check.scores, check.flags, check.bands = res.scores, res.flags, res.bands
+            check.lengths = lengths
+        return check
 
     def predict_what_if(self, synthesizer, traffic_plan, step_size: int,
                         rng=None) -> Dict[str, np.ndarray]:
