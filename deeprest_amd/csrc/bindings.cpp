@@ -55,10 +55,12 @@ void dr_fused_adam_dev(const int64_t* meta, int nt, int64_t total,
                        hipStream_t stream);
 // the dr_gru_* entries return the HIP error of their set-up or launches, 0 on
 // success (gru_launch_check below)
+int dr_gru_fwd_fuses_heads(int B, int C);
 int dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
                const void* w_hh, const float* b_hh, const void* h0, void* h_all,
-               void* saves, int B, int TT, int C, int reverse, int save,
-               int fp8, int is_bf16, hipStream_t stream);
+               void* saves, const void* wh_fwd, void* out, int O, int B, int TT,
+               int C, int reverse, int save, int fp8, int is_bf16,
+               hipStream_t stream);
 int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
                   const void* w_hh, const float* b_hh, const void* h0,
                   const void* wh_fwd, void* out, void* h_last, int B, int TT,
@@ -494,27 +496,64 @@ static void gru_forward_checks(const at::Tensor& xg, const at::Tensor& w_hh,
               "x_gates too large for 32-bit staging offsets");
 }
 
+// the (32, H) bf16 head weight image of the forward kernels' head phase
+static void check_wh_fwd(const at::Tensor& wh_fwd, int64_t O, int H) {
+  TORCH_CHECK(O >= 1 && O <= 32, "the fused head phase needs 1 <= O <= 32, got ", O);
+  TORCH_CHECK(wh_fwd.scalar_type() == at::kBFloat16 &&
+                  wh_fwd.sizes() == at::IntArrayRef({32, H}) &&
+                  wh_fwd.is_contiguous() && wh_fwd.is_cuda(),
+              "wh_fwd must be the (32, H) bf16 head weight image");
+}
+
+// Whether gru_seq_forward at these sizes takes wh_fwd and runs the head
+// projection inside the kernel; callers ask here, the launcher decides.
+bool gru_fwd_fuses_heads(int64_t B, int64_t C, bool save) {
+  return save && dr_gru_fwd_fuses_heads((int)B, (int)C) != 0;
+}
+
+// Returns {h_all, saves}.  With wh_fwd (the decode entry's head weight image)
+// and O, allowed only where gru_fwd_fuses_heads says so, the kernel runs the
+// head phase too and {h_all, saves, out} comes back, out (B, T, C, O) =
+// h_all @ w_head^T.
 std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
                                         at::Tensor b_hh, at::Tensor h0,
                                         at::Tensor gamma, at::Tensor beta,
-                                        bool reverse, bool save, bool fp8) {
+                                        bool reverse, bool save, bool fp8,
+                                        c10::optional<at::Tensor> wh_fwd,
+                                        int64_t O) {
   TORCH_CHECK(!(fp8 && save), "fp8 GRU path is inference-only (no saves)");
   const at::cuda::CUDAGuard guard(xg.device());
   gru_forward_checks(xg, w_hh, b_hh, h0, gamma, beta);
   int B = (int)xg.size(0), TT = (int)xg.size(1);
   int C = (int)h0.size(1), H = (int)h0.size(2);
+  TORCH_CHECK((int64_t)B * TT * C < (1LL << 31),
+              "gru forward: too many (b, t, c) rows for 32-bit row indices");
+  const bool heads = wh_fwd.has_value();
+  if (heads) {
+    TORCH_CHECK(!fp8 && gru_fwd_fuses_heads(B, C, save),
+                "gru forward: no in-kernel head phase at B=", B, " C=", C,
+                " save=", save, " (ask gru_fwd_fuses_heads first)");
+    check_wh_fwd(*wh_fwd, O, H);
+    TORCH_CHECK((int64_t)B * TT * C * O < (1LL << 31),
+                "head output too large for 32-bit store offsets");
+  }
   auto h_all = at::empty({B, TT, C, H}, xg.options());
   auto saves = save ? at::empty({B, TT, C, 2 * H}, xg.options())
                     : at::empty({0}, xg.options());
+  auto out = heads ? at::empty({B, TT, C, O}, xg.options())
+                   : at::empty({0}, xg.options());
   auto w_gemm = gru_w_gemm(w_hh);
   gru_launch_check(
       dr_gru_fwd(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                  w_gemm.data_ptr(), b_hh.data_ptr<float>(), h0.data_ptr(),
-                 h_all.data_ptr(), save ? saves.data_ptr() : nullptr, B, TT, C,
+                 h_all.data_ptr(), save ? saves.data_ptr() : nullptr,
+                 heads ? wh_fwd->data_ptr() : nullptr,
+                 heads ? out.data_ptr() : nullptr, heads ? (int)O : 0, B, TT, C,
                  reverse ? 1 : 0, save ? 1 : 0, fp8 ? 1 : 0, is_bf16(xg),
                  cur_stream()),
       "gru forward");
-  return {h_all, saves};
+  if (!heads) return {h_all, saves};
+  return {h_all, saves, out};
 }
 
 // Inference decode: the GRU sequence with the quantile-head projection done
@@ -534,11 +573,7 @@ std::vector<at::Tensor> gru_seq_decode(at::Tensor xg, at::Tensor w_hh,
   gru_forward_checks(xg, w_hh, b_hh, h0, gamma, beta);
   int B = (int)xg.size(0), TT = (int)xg.size(1);
   int C = (int)h0.size(1), H = (int)h0.size(2);
-  TORCH_CHECK(O >= 1 && O <= 32, "fused head decode needs 1 <= O <= 32, got ", O);
-  TORCH_CHECK(wh_fwd.scalar_type() == at::kBFloat16 &&
-                  wh_fwd.sizes() == at::IntArrayRef({32, H}) &&
-                  wh_fwd.is_contiguous() && wh_fwd.is_cuda(),
-              "wh_fwd must be the (32, H) bf16 head weight image");
+  check_wh_fwd(wh_fwd, O, H);
   TORCH_CHECK((int64_t)B * TT * C * O < (1LL << 31),
               "decode output too large for 32-bit store offsets");
   const int* lens = lengths_ptr(lengths, xg, B, "gru decode lengths");
@@ -829,7 +864,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_adam_capturable", &fused_adam_capturable);
   m.def("gru_seq_forward", &gru_seq_forward, py::arg("xg"), py::arg("w_hh"),
         py::arg("b_hh"), py::arg("h0"), py::arg("gamma"), py::arg("beta"),
-        py::arg("reverse"), py::arg("save"), py::arg("fp8") = false);
+        py::arg("reverse"), py::arg("save"), py::arg("fp8") = false,
+        py::arg("wh_fwd") = py::none(), py::arg("O") = 0);
+  m.def("gru_fwd_fuses_heads", &gru_fwd_fuses_heads, py::arg("B"), py::arg("C"),
+        py::arg("save"));
   m.def("gru_seq_decode", &gru_seq_decode, py::arg("xg"), py::arg("w_hh"),
         py::arg("b_hh"), py::arg("h0"), py::arg("gamma"), py::arg("beta"),
         py::arg("wh_fwd"), py::arg("O"), py::arg("reverse"), py::arg("fp8") = false,

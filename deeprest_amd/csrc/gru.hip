@@ -43,7 +43,7 @@ constexpr int WAVES = 4;
 constexpr int THREADS = WAVES * DR_WAVE;
 constexpr int KT = H / 32;    // K-tiles of 32 in the fwd GEMM (4)
 constexpr int NT = G3H / 16;  // N-tiles of 16 (24)
-constexpr int XG_SLOTS = 32;  // distinct batch indices a 64-row tile may span
+constexpr int XG_SLOTS = 32;  // xg staging slots: waves x batches a wave's 16 rows span
 
 constexpr int LDS_MAX = 163840;  // dynamic LDS one workgroup may declare
 
@@ -104,6 +104,16 @@ __device__ __forceinline__ int swz768(int row, int k_elem) {
 
 __device__ __forceinline__ bf16x8 lds_read8(const char* base, int byte_off) {
   return *reinterpret_cast<const bf16x8*>(base + byte_off);
+}
+
+// Orders ONE wave's own LDS accesses: what some lanes wrote before it, other
+// lanes of the same wave may read after it.  The hardware executes a wave's
+// LDS operations in issue order, so a wavefront-scope fence costs no
+// instruction and no wait; it only pins the compiler's ordering.
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---- pi-layout vector IO: 8 lane-owned values <-> 16/32 contiguous bytes ----
@@ -190,13 +200,20 @@ __device__ __forceinline__ bf16x8 ld_frag<float>(const float* src) {
 // NSUB = 2: 8 waves / 128-row tile — 2 waves/SIMD (the kernel is
 // latency-stalled at 1 wave/SIMD); gamma/beta/b_hh then stream from L1/L2
 // instead of registers so each wave fits the 256-reg budget.
-// HEADS = true (inference decode, SAVE = false): h_all is never written.
-// After each step's epilogue every wave multiplies its own 16 rows of the h
-// mirror by the quantile heads' weight image wh_fwd (32, H) bf16 —
-// wh_fwd[o][k] = w_head[o][k], exact zero rows for o >= O — on two more
-// 16-wide N-tiles and stores out (B, TT, C, O); the state after the last
-// processed step goes to h_last (B, C, H).  The image sits in LDS as 32 more
-// 256-byte rows behind the W image (8 KB, same swizzle, whatever FP8 is).
+// Wave ownership: a wave's A-fragments, epilogue, head phase and h_all store
+// touch only its own 16 rows of the h mirror, and it stages x_gates for the
+// batches of those rows into its own slots of the XG region.  After the
+// prologue the waves of a block share nothing they write, so the time loop
+// has no workgroup barrier and the waves free-run (as in the backward).
+// HEADS = true: after each step's epilogue every wave multiplies its own 16
+// rows of the h mirror by the quantile heads' weight image wh_fwd (32, H)
+// bf16 — wh_fwd[o][k] = w_head[o][k], exact zero rows for o >= O — on two
+// more 16-wide N-tiles and stores out (B, TT, C, O).  The image sits in LDS as
+// 32 more 256-byte rows behind the W image (8 KB, same swizzle, whatever FP8
+// is).  Inference decode (SAVE = false): h_all is never written and the state
+// after the last processed step goes to h_last (B, C, H).  Training forward
+// (SAVE = true, 8-wave tile only): saves, out and h_all are all written, and
+// there is no h_last.
 // VARLEN = true (HEADS only): batch b is valid at t < clamp(lens[b], 1, TT).
 // A row whose time index is padding HOLDS its state through a select on
 // hnew — whatever the padded xg holds, NaN included, is computed and thrown
@@ -226,8 +243,9 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     T* __restrict__ h_last,        // HEADS: (B, C, H)
     int O,
     const int* __restrict__ lens) {  // VARLEN: (B,) int32
-  static_assert(!(HEADS && SAVE), "the head phase is inference-only");
   static_assert(HEADS || !VARLEN, "per-row lengths exist in the decode kernel only");
+  static_assert(!(SAVE && (VARLEN || FP8)),
+                "the saving kernels run full windows on bf16 GEMM tiles");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using L = FwdLds<FP8, NSUB, HEADS>;
   constexpr int BROWS = ROWS * NSUB;           // rows per block
@@ -244,7 +262,6 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
   const int lane = tid % DR_WAVE;
   const int64_t R = (int64_t)B * C;
   const int64_t r0 = (int64_t)blockIdx.x * BROWS;
-  const int b_lo = (int)(r0 / C);
 
   // ---- prologue: stage the W image into swizzled LDS ----
   for (int id = tid; id < G3H * (H / 8); id += BTHREADS) {
@@ -351,59 +368,44 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
   const int t_first = reverse ? (TT - 1) : 0;
   const int dirC = (reverse ? -1 : 1) * C;           // row-index per-t stride
 
-  // xg staging chunks owned by this thread (slot, blk fixed over t);
-  // offsets are 32-bit (binding checks xg.numel() < 2^31)
-  constexpr int MAXCH = 6;  // covers n_b <= 32 slots at 256 threads
+  // xg staging, per wave: wave wv stages only the batches its own 16 rows
+  // span, into its own WSLOTS slots of the XG region, so the time loop needs
+  // no workgroup barrier.  16 consecutive rows span at most ceil(15/C)+1
+  // batches: 6 at C >= 3 (4 waves x 6 slots), 4 at C >= 5, the 8-wave
+  // variant's dispatch condition (8 waves x 4 slots).  The chunks (slot, blk
+  // fixed over t) are dealt over the wave's 64 lanes; offsets are 32-bit
+  // (binding checks xg.numel() < 2^31).
+  constexpr int WSLOTS = NSUB == 2 ? 4 : 6;
+  static_assert(WAVES * NSUB * WSLOTS <= XG_SLOTS,
+                "per-wave xg slots exceed the XG region");
+  constexpr int MAXCH = (WSLOTS * (G3H / 8) + DR_WAVE - 1) / DR_WAVE;  // 3 or 5
+  const int b_wlo = (int)(std::min<int64_t>(r0 + wv * 16, R - 1) / C);
   int stage_soff[MAXCH];    // xg element offset at t_first
   int stage_pi0[MAXCH];     // pi-layout LDS element offset of the chunk
   int n_stage = 0;
   {
-    int n_b = (int)(std::min<int64_t>(r0 + BROWS - 1, R - 1) / C) - b_lo + 1;
-    for (int id = tid; id < n_b * (G3H / 8) && n_stage < MAXCH; id += BTHREADS) {
+    int n_b = (int)(std::min<int64_t>(r0 + wv * 16 + 15, R - 1) / C) - b_wlo + 1;
+    n_b = std::min(n_b, WSLOTS);   // never binds under the dispatch conditions;
+                                   // keeps every LDS index inside the wave's slots
+    for (int id = lane; id < n_b * (G3H / 8) && n_stage < MAXCH; id += DR_WAVE) {
       int slot = id / (G3H / 8);
       int blk = id % (G3H / 8);
       int j0 = blk * 8;
       int g = j0 >> 7;
       int col0 = j0 & 127;
-      stage_soff[n_stage] = (int)((((int64_t)(b_lo + slot) * TT) + t_first) * G3H) + j0;
+      stage_soff[n_stage] = (int)((((int64_t)(b_wlo + slot) * TT) + t_first) * G3H) + j0;
       stage_pi0[n_stage] =
-          slot * G3H + g * H + ((col0 & 15) << 3) + (col0 >> 4);
+          (wv * WSLOTS + slot) * G3H + g * H + ((col0 & 15) << 3) + (col0 >> 4);
       ++n_stage;
     }
   }
-  // h_all cooperative store chunks (4 per thread; row index fixed over t);
-  // HEADS has no h_all store, so nothing is filled in
-  int64_t hout_bc[4];       // (b*TT + t_first)*C + c
-  int hout_blk[4];
-  int hout_lds[4];
-  bool hout_live[4];
-  if constexpr (!HEADS) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      int id = tid + u * BTHREADS;            // BROWS*(H/8) = 4*BTHREADS
-      int row = id / (H / 8);
-      int blk = id % (H / 8);
-      int64_t r = r0 + row;
-      hout_live[u] = r < R;
-      int64_t rr = hout_live[u] ? r : (R - 1);
-      int b = (int)(rr / C), c = (int)(rr % C);
-      hout_bc[u] = ((int64_t)b * TT + t_first) * C + c;
-      hout_blk[u] = blk * 8;
-      hout_lds[u] = FP8 ? (row * 128 + ((blk ^ (row & 15)) << 3))
-                        : (row * 256 + ((blk ^ (row & 15)) << 4));
-    }
-  }
-  // per-lane-row indices for the saves stores (pi layout)
-  int64_t sv_bc[4];
+  // ONE 32-bit row index per lane row, (b*TT + t_first)*C + c, shared by the
+  // saves, h_all and out stores and widened at the multiply (the binding
+  // checks B*TT*C < 2^31 and, with heads, B*TT*C*O < 2^31)
+  int bc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    sv_bc[i] = ((int64_t)b_of[i] * TT + t_first) * C + comp_of[i];
-  // HEADS: the same row indices for the out stores, 32-bit (the binding
-  // checks out.numel() < 2^31)
-  int out_bc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    out_bc[i] = (b_of[i] * TT + t_first) * C + comp_of[i];
+    bc[i] = (b_of[i] * TT + t_first) * C + comp_of[i];
   // per-wave A-fragment LDS offsets
   int afrag_off[KT];
   {
@@ -413,19 +415,28 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     for (int kt = 0; kt < KT; ++kt)
       afrag_off[kt] = FP8 ? swz8(arow, kt * 32 + k0) : swz(arow, kt * 32 + k0);
   }
-  // xg LDS row bases (pi layout, element-indexed)
+  // xg LDS row bases in the wave's own slots (pi layout, element-indexed).
+  // Keep the operand order: with c_col * 8 added first the spilling FP8 tile
+  // came out at 176 B of scratch instead of 76 / 92.
   const uint16_t* xg_rows[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    xg_rows[i] = reinterpret_cast<const uint16_t*>(XGl) +
-                 (b_of[i] - b_lo) * G3H + c_col * 8;
+    xg_rows[i] =
+        reinterpret_cast<const uint16_t*>(XGl) +
+        (wv * WSLOTS + std::min(b_of[i] - b_wlo, WSLOTS - 1)) * G3H + c_col * 8;
 
-  __syncthreads();
+  __syncthreads();   // W / wh_fwd staging visible to all waves
 
-  // ---- time loop ----
+  // ---- time loop: no workgroup barrier inside ----
+  // Everything a wave reads from the h mirror and the XG region it wrote
+  // itself: its A-fragments, head fragments and h_all chunks are its own 16
+  // mirror rows, its xg_rows its own slots.  A wave's LDS operations execute
+  // in issue order, so its own write-then-read needs no s_barrier; the
+  // wavefront-scope fences below only keep the compiler from moving those
+  // accesses across each other.  Waves free-run: one wave's MFMA / LDS phase
+  // overlaps the other wave's epilogue on the same SIMD.
   int stage_toff = 0;                        // += dir*G3H per step (32-bit)
-  int64_t bc_toff = 0;                       // += dirC per step (row-index units)
-  int out_toff = 0;                          // HEADS: the same, 32-bit
+  int bc_toff = 0;                           // += dirC per step (row-index units)
   const int stage_tstep = (reverse ? -1 : 1) * G3H;
   for (int step = 0; step < TT; ++step) {
     // VARLEN: row i is active at this step iff t_now < len_of[i]
@@ -456,7 +467,10 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
         for (int e = 0; e < 8; ++e) dst[e * 8] = vals[e];
       }
     }
-    __syncthreads();
+    // the slot writes above stay ahead of this step's epilogue reads (other
+    // lanes of this wave read them), and this step's mirror writes behind the
+    // previous step's h_all / head reads
+    wave_lds_fence();
 
     // ---- MFMA: hh = h_tile @ W^T -> (64, 384), this wave's 16 rows ----
     f32x4 acc[NT];
@@ -550,14 +564,17 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
       if (SAVE && live[i]) {
         // only r and z are saved (2H); the backward recomputes n and hh_n
         // (an extra H x H GEMM there is cheaper than 2H of HBM both ways)
-        T* sv = saves + (sv_bc[i] + bc_toff) * (2 * H) + c_col * 8;
+        T* sv = saves + (int64_t)(bc[i] + bc_toff) * (2 * H) + c_col * 8;
         st8(sv, fr);
         st8(sv + H, fz);
       }
       // fence: stop the scheduler interleaving all 4 rows' live ranges
       __builtin_amdgcn_sched_barrier(0);
     }
-    __syncthreads();
+    // the mirror rows written above are read below and at the top of the next
+    // step by other lanes of this wave; the next step's slot writes stay
+    // behind the xg reads above
+    wave_lds_fence();
 
     if constexpr (HEADS) {
       // ---- head phase: out[rows, t, :O] = h_t @ w_head^T ----
@@ -598,24 +615,22 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
 #pragma unroll
             for (int i = 0; i < 4; ++i)
               if (live[i] && (!VARLEN || t_now < len_of[i]))
-                stf(out + (out_bc[i] + out_toff) * O + j, a[i]);
+                stf(out + (bc[i] + bc_toff) * O + j, a[i]);
           }
         }
       }
-      stage_toff += stage_tstep;
-      out_toff += dirC;
-      // no end-of-step barrier: a wave's h-mirror rows are written and read
-      // by that wave alone once the cooperative h_all store is gone, and the
-      // next xg staging is ordered behind every wave's epilogue reads by the
-      // barrier above.
-    } else {
-      // ---- cooperative vectorized h_all store (reads the bf16 LDS tile) ----
+    }
+    if constexpr (!HEADS || SAVE) {
+      // ---- h_all store: lane (rgrp, c_col) stores chunk c_col (8 values) of
+      // its own 4 rows from the mirror; 16 lanes cover one row ----
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        if (hout_live[u]) {
-          T* dst = h_all + (hout_bc[u] + bc_toff) * H + hout_blk[u];
+        if (live[u]) {
+          T* dst = h_all + (int64_t)(bc[u] + bc_toff) * H + c_col * 8;
+          const int row = row_of[u];
           if constexpr (FP8) {
-            uint64_t raw = *reinterpret_cast<const uint64_t*>(Hl + hout_lds[u]);
+            uint64_t raw = *reinterpret_cast<const uint64_t*>(
+                Hl + row * 128 + ((c_col ^ (row & 15)) << 3));
             const uint8_t* q = reinterpret_cast<const uint8_t*>(&raw);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -624,19 +639,18 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
               stf(dst + e, float(x));
             }
           } else {
-            st_frag(dst, lds_read8(Hl, hout_lds[u]));
+            st_frag(dst, lds_read8(Hl, row * 256 + ((c_col ^ (row & 15)) << 4)));
           }
         }
       }
-      stage_toff += stage_tstep;
-      bc_toff += dirC;
-      // barrier covers both: h-store reads done AND next step's a-frag reads
-      // see the same consistent tile until the next epilogue writes it.
-      __syncthreads();
     }
+    stage_toff += stage_tstep;
+    bc_toff += dirC;
+    // no end-of-step barrier: the next epilogue's mirror writes follow the
+    // reads above in this wave's own issue order (fence at the next staging)
   }
 
-  if constexpr (HEADS) {
+  if constexpr (HEADS && !SAVE) {
     // ---- h_last: the fp32 register state, rounded once to the IO dtype ----
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -1355,13 +1369,18 @@ template <typename F>
 static hipError_t with_fwd_tile(int B, int C, int fp8, F&& f) {
   const int64_t tiles128 = ((int64_t)B * C + 2 * ROWS - 1) / (2 * ROWS);
   // 8-wave 128-row variant: 2 waves/SIMD.  It needs enough tiles to fill the
-  // chip at one block per CU, and C >= 5: its 128 rows must not span more
-  // than XG_SLOTS batch indices (C = 4 spans up to 33).
+  // chip at one block per CU, and C >= 5: a wave's 16 rows must not span more
+  // than its 4 xg staging slots (C = 4 spans up to 5 batch indices).
   const bool wide = !fp8 && tiles128 >= 192 && C >= 5;
   if (!wide && !fp8) return f(FwdTile<false, 1>{});
   if (fp8) return f(FwdTile<true, 1>{});
   return f(FwdTile<false, 2>{});
 }
+// Whether the training forward (SAVE) runs the head phase in the kernel: on
+// the 8-wave tile only (its 4-wave twin spills).  The one place that decides;
+// the sequence entry and dr_gru_fwd_fuses_heads both ask here.
+template <typename Tile>
+static constexpr bool fwd_train_heads(Tile) { return !Tile::FP8 && Tile::NSUB == 2; }
 
 // Raises a kernel's dynamic-LDS limit.  Each launch function keeps the result
 // in a function-local static: set once per instantiation (thread-safe, and
@@ -1380,8 +1399,8 @@ struct FwdArgs {
   const void* h0;
   void *h_all, *saves;     // sequence entry (saves: SAVE only); decode: null
   int B, TT, C, reverse;
-  const void* wh_fwd;      // decode entry; sequence: null / 0
-  void *out, *h_last;
+  const void* wh_fwd;      // head phase (decode, SAVE+HEADS); otherwise null / 0
+  void *out, *h_last;      // h_last: decode entry only
   int O;
   const int* lens;         // VARLEN only
   hipStream_t stream;
@@ -1509,16 +1528,39 @@ static hipError_t gru_reduce_launch(const void* dpre, const void* gamma,
 
 extern "C" {
 
+// 1 when a saving forward at (B, C) runs the quantile-head projection inside
+// the kernel (dr_gru_fwd then takes wh_fwd / out / O), 0 when the caller does
+// the projection itself.
+int dr_gru_fwd_fuses_heads(int B, int C) {
+  bool fuses = false;
+  (void)dr::with_fwd_tile(B, C, 0, [&](auto tile) {
+    fuses = dr::fwd_train_heads(tile);
+    return hipSuccess;
+  });
+  return fuses ? 1 : 0;
+}
+
+// wh_fwd != nullptr (save only, where dr_gru_fwd_fuses_heads says so): the
+// (32, H) bf16 head weight image of dr_gru_decode; the kernel also writes
+// out (B, TT, C, O).
 int dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
                const void* w_hh, const float* b_hh, const void* h0, void* h_all,
-               void* saves, int B, int TT, int C, int reverse, int save,
-               int fp8, int is_bf16, hipStream_t stream) {
+               void* saves, const void* wh_fwd, void* out, int O, int B, int TT,
+               int C, int reverse, int save, int fp8, int is_bf16,
+               hipStream_t stream) {
+  const bool heads = wh_fwd != nullptr;
   const dr::FwdArgs a{xg, gamma, beta, w_hh, b_hh, h0, h_all, saves, B, TT, C,
-                      reverse, nullptr, nullptr, nullptr, 0, nullptr, stream};
+                      reverse, wh_fwd, out, nullptr, heads ? O : 0, nullptr, stream};
+  if (heads && !save) return (int)hipErrorInvalidValue;
   return (int)dr::with_io_type(is_bf16, [&](auto io) {
     using T = typename decltype(io)::type;
     return dr::with_fwd_tile(B, C, fp8, [&](auto tile) {
       using V = decltype(tile);
+      if constexpr (dr::fwd_train_heads(V{})) {
+        if (heads) return dr::gru_fwd_launch<T, true, false, V::NSUB, true, false>(a);
+      } else {
+        if (heads) return hipErrorInvalidValue;
+      }
       // the fp8 tiles are inference-only: no SAVE instantiation exists
       if constexpr (!V::FP8)
         if (save) return dr::gru_fwd_launch<T, true, false, V::NSUB, false, false>(a);

@@ -227,22 +227,39 @@ def _bwd_reductions(ext, dpre, dh0, x_gates, w_hh, h0, gamma, h_all, reverse):
 HEAD_FUSE_MAX_OUT = 32    # one K=32 MFMA covers the heads' output width
 
 
+def _head_image_fwd(w_head):
+    """(32, H) bf16 B-operand image of the forward kernels' head phase:
+    w_head (O, H) rounded to bf16 and zero-padded along the output axis."""
+    wh_fwd = torch.zeros(32, w_head.shape[1], device=w_head.device,
+                         dtype=torch.bfloat16)
+    wh_fwd[:w_head.shape[0]] = w_head
+    return wh_fwd
+
+
 class _FusedGRUHeads(torch.autograd.Function):
     """GRU sequence + quantile-head projection as one autograd node, so the
     backward never materializes the (B, T, C, H) head input gradient: the
-    kernel rebuilds grad_part @ w_head per step on the matrix unit."""
+    kernel rebuilds grad_part @ w_head per step on the matrix unit.  Where
+    the saving forward kernel has a head phase (the binding knows), the
+    forward projection runs per step inside it too."""
 
     @staticmethod
     def forward(ctx, x_gates, w_hh, b_hh, h0, gamma, beta, w_head, reverse):
         ext = require_native("fused_gru_heads")
         need_grad = any(ctx.needs_input_grad)
-        h_all, saves = ext.gru_seq_forward(
-            x_gates, w_hh, b_hh, h0, gamma, beta, bool(reverse), bool(need_grad)
-        )
-        B, T, C, H = h_all.shape
-        # same GEMM as ops/linear_bigk.py's forward (3-D, leading-dim batch)
-        w = w_head.to(h_all.dtype)
-        part = torch.matmul(h_all.reshape(B, T * C, H), w.t())
+        args = (x_gates, w_hh, b_hh, h0, gamma, beta, bool(reverse), bool(need_grad))
+        w = w_head.to(x_gates.dtype)
+        B, C, H = h0.shape
+        T = x_gates.shape[1]
+        if ext.gru_fwd_fuses_heads(B, C, bool(need_grad)):
+            # the kernel projects each step's h onto the heads itself (w_head
+            # rounded to bf16, as in fused_gru_decode): h_all is not read back
+            h_all, saves, part = ext.gru_seq_forward(
+                *args, False, _head_image_fwd(w), w.shape[0])
+        else:
+            h_all, saves = ext.gru_seq_forward(*args)
+            # same GEMM as ops/linear_bigk.py's forward (3-D, leading-dim batch)
+            part = torch.matmul(h_all.reshape(B, T * C, H), w.t())
         ctx.save_for_backward(x_gates, w_hh, b_hh, h0, gamma, beta, h_all, saves, w)
         ctx.reverse = bool(reverse)
         ctx.w_head_dtype = w_head.dtype
@@ -431,12 +448,8 @@ def fused_gru_decode(
         out = torch.nn.functional.linear(h_all, w_head.to(h_all.dtype))
         return out, h_last
     ext = require_native("fused_gru_decode")
-    O = w_head.shape[0]
-    # (32, H) bf16 B-operand image: w_head zero-padded along the output axis
-    wh_fwd = torch.zeros(32, w_head.shape[1], device=x_gates.device,
-                         dtype=torch.bfloat16)
-    wh_fwd[:O] = w_head
     out, h_last = ext.gru_seq_decode(
         *_kernel_operands(x_gates, w_hh, b_hh, h0, gamma, beta),
-        wh_fwd, O, bool(reverse), bool(fp8), lengths)
+        _head_image_fwd(w_head), w_head.shape[0], bool(reverse), bool(fp8),
+        lengths)
     return out, h_last
