@@ -13,13 +13,6 @@
 
 // ---- C ABI launchers from the .hip translation units ----
 extern "C" {
-void dr_layernorm_fwd(const void* x, const float* w, const float* b, void* y,
-                      float* mean, float* rstd, int64_t n_rows, int D, float eps,
-                      int is_bf16, hipStream_t stream);
-void dr_layernorm_bwd(const void* dy, const void* x, const float* w,
-                      const float* mean, const float* rstd, void* dx,
-                      float* dwdb_part, int n_blocks, int64_t n_rows, int D,
-                      int is_bf16, hipStream_t stream);
 void dr_dropout_add_ln_fwd(const void* branch, const void* residual, const float* w,
                            const float* b, const int64_t* seed, uint32_t thr,
                            float scale, void* r_out, void* normed, float* mean,
@@ -123,45 +116,6 @@ const int* lengths_ptr(const c10::optional<at::Tensor>& lengths,
   return l.data_ptr<int>();
 }
 
-// ------------------------------------------------------------- layer norm
-std::vector<at::Tensor> layer_norm_forward(at::Tensor x, at::Tensor w, at::Tensor b,
-                                           double eps) {
-  const at::cuda::CUDAGuard guard(x.device());
-  check_dtype(x, "x");
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && b.is_contiguous());
-  TORCH_CHECK(w.scalar_type() == at::kFloat && b.scalar_type() == at::kFloat,
-              "layer_norm weight/bias must be f32");
-  int D = (int)x.size(-1);
-  int64_t n_rows = x.numel() / D;
-  TORCH_CHECK(w.numel() == D && b.numel() == D);
-  auto y = at::empty_like(x);
-  auto mean = at::empty({n_rows}, x.options().dtype(at::kFloat));
-  auto rstd = at::empty({n_rows}, x.options().dtype(at::kFloat));
-  dr_layernorm_fwd(x.data_ptr(), w.data_ptr<float>(), b.data_ptr<float>(),
-                   y.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                   n_rows, D, (float)eps, is_bf16(x), cur_stream());
-  return {y, mean, rstd};
-}
-
-std::vector<at::Tensor> layer_norm_backward(at::Tensor dy, at::Tensor x, at::Tensor w,
-                                            at::Tensor mean, at::Tensor rstd) {
-  const at::cuda::CUDAGuard guard(x.device());
-  TORCH_CHECK(dy.is_contiguous() && x.is_contiguous());
-  TORCH_CHECK(dy.scalar_type() == x.scalar_type());
-  int D = (int)x.size(-1);
-  int64_t n_rows = x.numel() / D;
-  int n_blocks = (int)std::min<int64_t>((n_rows + 3) / 4, 1024);
-  if (n_blocks == 0) n_blocks = 1;
-  auto dx = at::empty_like(x);
-  auto part = at::zeros({n_blocks, 2, D}, x.options().dtype(at::kFloat));
-  dr_layernorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr<float>(),
-                   mean.data_ptr<float>(), rstd.data_ptr<float>(), dx.data_ptr(),
-                   part.data_ptr<float>(), n_blocks, n_rows, D, is_bf16(x),
-                   cur_stream());
-  auto sums = part.sum(0);  // (2, D)
-  return {dx, sums[0], sums[1]};
-}
-
 // ------------------------------------------- dropout + residual + layer norm
 // seed absent: no mask (p == 0 or eval).  w/b absent: plain dropout_add.
 struct DropoutArgs {
@@ -189,57 +143,67 @@ DropoutArgs dropout_args(const c10::optional<at::Tensor>& seed, double p,
   return a;
 }
 
-std::vector<at::Tensor> dropout_add_ln_forward(at::Tensor branch, at::Tensor residual,
+// branch absent: plain layer_norm(residual); needs w/b, takes no seed, and
+// returns an empty r_out (the row is not copied).
+std::vector<at::Tensor> dropout_add_ln_forward(c10::optional<at::Tensor> branch,
+                                               at::Tensor residual,
                                                c10::optional<at::Tensor> w,
                                                c10::optional<at::Tensor> b,
                                                c10::optional<at::Tensor> seed,
                                                double p, double eps) {
-  const at::cuda::CUDAGuard guard(branch.device());
-  check_dtype(branch, "branch");
-  TORCH_CHECK(branch.is_cuda() && residual.device() == branch.device());
-  TORCH_CHECK(residual.scalar_type() == branch.scalar_type() &&
-                  residual.sizes() == branch.sizes(),
-              "branch and residual must agree in dtype and shape");
-  TORCH_CHECK(branch.is_contiguous() && residual.is_contiguous());
-  TORCH_CHECK(branch.dim() >= 1 && branch.size(-1) > 0);
-  const bool has_norm = w.has_value();
+  const at::cuda::CUDAGuard guard(residual.device());
+  check_dtype(residual, "residual");
+  TORCH_CHECK(residual.is_cuda() && residual.is_contiguous());
+  TORCH_CHECK(residual.dim() >= 1 && residual.size(-1) > 0);
+  const bool has_add = branch.has_value(), has_norm = w.has_value();
   TORCH_CHECK(b.has_value() == has_norm, "weight and bias go together");
-  int D = (int)branch.size(-1);
-  int64_t n_rows = branch.numel() / D;
-  DropoutArgs da = dropout_args(seed, p, branch);
-  auto r_out = at::empty_like(branch);
-  auto f32 = branch.options().dtype(at::kFloat);
+  if (has_add) {
+    TORCH_CHECK(branch->device() == residual.device() && branch->is_contiguous());
+    TORCH_CHECK(branch->scalar_type() == residual.scalar_type() &&
+                    branch->sizes() == residual.sizes(),
+                "branch and residual must agree in dtype and shape");
+  } else {
+    TORCH_CHECK(has_norm && !seed.has_value(),
+                "without a branch the op is layer_norm: weight/bias, no seed");
+  }
+  int D = (int)residual.size(-1);
+  int64_t n_rows = residual.numel() / D;
+  DropoutArgs da = dropout_args(seed, p, residual);
+  auto r_out = has_add ? at::empty_like(residual) : at::empty({0}, residual.options());
+  auto f32 = residual.options().dtype(at::kFloat);
   at::Tensor normed, mean, rstd;
   if (has_norm) {
     TORCH_CHECK(w->is_contiguous() && b->is_contiguous());
     TORCH_CHECK(w->scalar_type() == at::kFloat && b->scalar_type() == at::kFloat,
                 "layer_norm weight/bias must be f32");
-    TORCH_CHECK(w->device() == branch.device() && b->device() == branch.device());
+    TORCH_CHECK(w->device() == residual.device() && b->device() == residual.device());
     TORCH_CHECK(w->numel() == D && b->numel() == D);
-    normed = at::empty_like(branch);
+    normed = at::empty_like(residual);
     mean = at::empty({n_rows}, f32);
     rstd = at::empty({n_rows}, f32);
   } else {
-    normed = at::empty({0}, branch.options());
+    normed = at::empty({0}, residual.options());
     mean = at::empty({0}, f32);
     rstd = at::empty({0}, f32);
   }
   if (n_rows > 0)
-    dr_dropout_add_ln_fwd(branch.data_ptr(), residual.data_ptr(),
+    dr_dropout_add_ln_fwd(has_add ? branch->data_ptr() : nullptr, residual.data_ptr(),
                           has_norm ? w->data_ptr<float>() : nullptr,
                           has_norm ? b->data_ptr<float>() : nullptr, da.seed,
-                          da.thr, da.scale, r_out.data_ptr(),
+                          da.thr, da.scale, has_add ? r_out.data_ptr() : nullptr,
                           has_norm ? normed.data_ptr() : nullptr,
                           has_norm ? mean.data_ptr<float>() : nullptr,
                           has_norm ? rstd.data_ptr<float>() : nullptr, n_rows, D,
-                          (float)eps, is_bf16(branch), cur_stream());
+                          (float)eps, is_bf16(residual), cur_stream());
   return {r_out, normed, mean, rstd};
 }
 
 // returns {d_residual, d_branch, dw, db}; without a mask d_branch IS
-// d_residual, without a norm d_residual IS d_r_out and dw/db are empty
+// d_residual, without a norm d_residual IS d_r_out and dw/db are empty.
+// d_r_out absent: layer_norm backward, r_out is its x and d_residual its dx.
 std::vector<at::Tensor> dropout_add_ln_backward(c10::optional<at::Tensor> d_normed,
-                                                at::Tensor d_r_out, at::Tensor r_out,
+                                                c10::optional<at::Tensor> d_r_out,
+                                                at::Tensor r_out,
                                                 c10::optional<at::Tensor> w,
                                                 c10::optional<at::Tensor> mean,
                                                 c10::optional<at::Tensor> rstd,
@@ -247,10 +211,16 @@ std::vector<at::Tensor> dropout_add_ln_backward(c10::optional<at::Tensor> d_norm
                                                 double p) {
   const at::cuda::CUDAGuard guard(r_out.device());
   check_dtype(r_out, "r_out");
-  TORCH_CHECK(d_r_out.is_cuda() && d_r_out.is_contiguous() && r_out.is_contiguous());
-  TORCH_CHECK(d_r_out.scalar_type() == r_out.scalar_type() &&
-              d_r_out.sizes() == r_out.sizes());
-  const bool has_norm = w.has_value();
+  TORCH_CHECK(r_out.is_cuda() && r_out.is_contiguous());
+  const bool has_add = d_r_out.has_value(), has_norm = w.has_value();
+  if (has_add) {
+    TORCH_CHECK(d_r_out->device() == r_out.device() && d_r_out->is_contiguous());
+    TORCH_CHECK(d_r_out->scalar_type() == r_out.scalar_type() &&
+                d_r_out->sizes() == r_out.sizes());
+  } else {
+    TORCH_CHECK(has_norm && !seed.has_value(),
+                "without d_r_out the op is layer_norm: weight, no seed");
+  }
   TORCH_CHECK(d_normed.has_value() == has_norm && mean.has_value() == has_norm &&
                   rstd.has_value() == has_norm,
               "d_normed, weight, mean and rstd go together");
@@ -259,10 +229,10 @@ std::vector<at::Tensor> dropout_add_ln_backward(c10::optional<at::Tensor> d_norm
   DropoutArgs da = dropout_args(seed, p, r_out);
   const bool has_mask = da.seed != nullptr;
   auto f32 = r_out.options().dtype(at::kFloat);
-  if (!has_norm && !has_mask) return {d_r_out, d_r_out, at::empty({0}, f32), at::empty({0}, f32)};
+  if (!has_norm && !has_mask) return {*d_r_out, *d_r_out, at::empty({0}, f32), at::empty({0}, f32)};
   int n_blocks = (int)std::min<int64_t>((n_rows + 3) / 4, 1024);
   if (n_blocks == 0) n_blocks = 1;
-  at::Tensor d_res = d_r_out, part;
+  at::Tensor d_res, part;
   if (has_norm) {
     TORCH_CHECK(d_normed->is_contiguous() && w->is_contiguous() &&
                 mean->is_contiguous() && rstd->is_contiguous());
@@ -272,14 +242,16 @@ std::vector<at::Tensor> dropout_add_ln_backward(c10::optional<at::Tensor> d_norm
     TORCH_CHECK(mean->scalar_type() == at::kFloat && mean->numel() == n_rows &&
                 rstd->scalar_type() == at::kFloat && rstd->numel() == n_rows);
     // dw/db partials live in 2 * D floats of dynamic LDS per block
-    TORCH_CHECK(D <= 8192, "dropout_add_layer_norm backward supports D <= 8192, got ", D);
+    TORCH_CHECK(D <= 8192, "layer_norm backward supports D <= 8192, got ", D);
     d_res = at::empty_like(r_out);
     part = at::zeros({n_blocks, 2, D}, f32);
+  } else {
+    d_res = *d_r_out;
   }
   at::Tensor d_branch = has_mask ? at::empty_like(r_out) : d_res;
   if (n_rows > 0)
     dr_dropout_add_ln_bwd(has_norm ? d_normed->data_ptr() : nullptr,
-                          d_r_out.data_ptr(), r_out.data_ptr(),
+                          has_add ? d_r_out->data_ptr() : nullptr, r_out.data_ptr(),
                           has_norm ? w->data_ptr<float>() : nullptr,
                           has_norm ? mean->data_ptr<float>() : nullptr,
                           has_norm ? rstd->data_ptr<float>() : nullptr, da.seed,
@@ -848,8 +820,6 @@ void register_featurize(py::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_featurize(m);
-  m.def("layer_norm_forward", &layer_norm_forward);
-  m.def("layer_norm_backward", &layer_norm_backward);
   m.def("dropout_add_ln_forward", &dropout_add_ln_forward, py::arg("branch"),
         py::arg("residual"), py::arg("weight"), py::arg("bias"), py::arg("seed"),
         py::arg("p"), py::arg("eps"));

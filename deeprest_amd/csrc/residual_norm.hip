@@ -4,14 +4,16 @@
 //   normed = LayerNorm(r_out) * w + b                    stats over the
 //                                                        ROUNDED r_out
 //
-// Same structure as layernorm.hip: one wave per row in a grid-stride row
-// loop, a vec4 path (lane owns 4 contiguous columns) for D % 4 == 0 &&
+// One wave per row in a grid-stride row loop, a vec4 path (lane owns 4
+// contiguous columns, w/b in registers across the row loop) for D % 4 == 0 &&
 // D <= 256 and a strided path for every other D.  The dropout mask is never
 // stored: it is Philox4x32-10 keyed on the ELEMENT index, so forward and
 // backward (and a CPU oracle) generate the same bits whatever the launch
 // geometry.  (key, stream) is read from device memory so a captured graph
 // sees fresh values on every replay.
 //
+// HAS_ADD off:  plain LayerNorm of `residual` (no branch, no r_out store, no
+//               d_r_out in backward); only with HAS_MASK off and HAS_NORM on.
 // HAS_MASK off: p == 0 or eval, no RNG work and no seed tensor.
 // HAS_NORM off: plain dropout_add (no stats, no w/b).
 #include "common.h"
@@ -71,7 +73,7 @@ template <> __device__ __forceinline__ float round_io<float>(float v) { return v
 template <> __device__ __forceinline__ float round_io<uint16_t>(float v) { return bf2f(f2bf(v)); }
 
 // ------------------------------------------------------------------ forward
-template <typename T, bool HAS_MASK, bool HAS_NORM>
+template <typename T, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
 __global__ void __launch_bounds__(256)
 dal_fwd_vec4(const T* __restrict__ branch, const T* __restrict__ residual,
              const float* __restrict__ w, const float* __restrict__ b,
@@ -95,10 +97,10 @@ dal_fwd_vec4(const T* __restrict__ branch, const T* __restrict__ residual,
   for (int64_t row = row0; row < n_rows; row += stride_rows) {
     const int64_t off = row * D + j0;   // D % 4 == 0: one Philox group
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (active) {
-      float a[4];
-      ld4(branch + off, a);
-      ld4(residual + off, v);
+    float a[4];
+    if (HAS_ADD && active) ld4(branch + off, a);
+    if (active) ld4(residual + off, v);
+    if (HAS_ADD && active) {
       if (HAS_MASK) {
         uint32_t o[4];
         philox4((uint64_t)off >> 2, pk, o);
@@ -137,7 +139,7 @@ dal_fwd_vec4(const T* __restrict__ branch, const T* __restrict__ residual,
 // Strided path for D <= 1024: lane owns columns lane, lane + 64, ...;
 // MAX_PER_LANE * 64 >= D.  The column loop is fully unrolled with a
 // wave-uniform exit so the per-lane values stay in registers.
-template <typename T, int MAX_PER_LANE, bool HAS_MASK, bool HAS_NORM>
+template <typename T, int MAX_PER_LANE, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
 __global__ void __launch_bounds__(256)
 dal_fwd_kernel(const T* __restrict__ branch, const T* __restrict__ residual,
                const float* __restrict__ w, const float* __restrict__ b,
@@ -163,14 +165,16 @@ dal_fwd_kernel(const T* __restrict__ branch, const T* __restrict__ residual,
       if (i * DR_WAVE >= D) break;
       const int j = lane + i * DR_WAVE;
       if (j < D) {
-        const float a = ldf(branch + base + j);
+        const float a = HAS_ADD ? ldf(branch + base + j) : 0.f;
         float r = ldf(residual + base + j);
-        if (HAS_MASK)
-          r += philox_keep1((uint64_t)(base + j), pk, thr) ? a * scale : 0.f;
-        else
-          r += a;
-        r = round_io<T>(r);
-        stf(r_out + base + j, r);
+        if (HAS_ADD) {
+          if (HAS_MASK)
+            r += philox_keep1((uint64_t)(base + j), pk, thr) ? a * scale : 0.f;
+          else
+            r += a;
+          r = round_io<T>(r);
+          stf(r_out + base + j, r);
+        }
         v[i] = r;
         s += r;
       }
@@ -203,7 +207,8 @@ dal_fwd_kernel(const T* __restrict__ branch, const T* __restrict__ residual,
 // D > 1024: nothing is held per lane.  Each lane re-reads the r_out values it
 // has just stored (same thread, same address: program order makes them
 // visible; they come back from L1/L2), so any D runs without scratch.
-template <typename T, bool HAS_MASK, bool HAS_NORM>
+// HAS_ADD off stores no r_out and re-reads the input row itself.
+template <typename T, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
 __global__ void __launch_bounds__(256)
 dal_fwd_stream(const T* __restrict__ branch, const T* __restrict__ residual,
                const float* __restrict__ w, const float* __restrict__ b,
@@ -223,22 +228,25 @@ dal_fwd_stream(const T* __restrict__ branch, const T* __restrict__ residual,
     const int64_t base = row * D;
     float s = 0.f;
     for (int j = lane; j < D; j += DR_WAVE) {
-      const float a = ldf(branch + base + j);
+      const float a = HAS_ADD ? ldf(branch + base + j) : 0.f;
       float r = ldf(residual + base + j);
-      if (HAS_MASK)
-        r += philox_keep1((uint64_t)(base + j), pk, thr) ? a * scale : 0.f;
-      else
-        r += a;
-      r = round_io<T>(r);
-      stf(r_out + base + j, r);
+      if (HAS_ADD) {
+        if (HAS_MASK)
+          r += philox_keep1((uint64_t)(base + j), pk, thr) ? a * scale : 0.f;
+        else
+          r += a;
+        r = round_io<T>(r);
+        stf(r_out + base + j, r);
+      }
       s += r;
     }
     if (HAS_NORM) {
+      const T* x = HAS_ADD ? r_out : residual;  // the row the stats are over
       s = wave_sum(s);
       const float mean = s / D;
       float var = 0.f;
       for (int j = lane; j < D; j += DR_WAVE) {
-        float d = ldf(r_out + base + j) - mean;
+        float d = ldf(x + base + j) - mean;
         var += d * d;
       }
       var = wave_sum(var) / D;
@@ -248,7 +256,7 @@ dal_fwd_stream(const T* __restrict__ branch, const T* __restrict__ residual,
         rstd_out[row] = rstd;
       }
       for (int j = lane; j < D; j += DR_WAVE)
-        stf(normed + base + j, (ldf(r_out + base + j) - mean) * rstd * w[j] + b[j]);
+        stf(normed + base + j, (ldf(x + base + j) - mean) * rstd * w[j] + b[j]);
     }
   }
 }
@@ -259,9 +267,11 @@ dal_fwd_stream(const T* __restrict__ branch, const T* __restrict__ residual,
 //   d_branch   = d_total * keep / (1 - p)      (mask regenerated)
 // d_res is written only with HAS_NORM (otherwise d_residual IS d_r_out) and
 // d_branch only with HAS_MASK (otherwise it equals d_residual).
-// dw/db as in ln_bwd_vec4: registers across the row loop, one LDS combine per
-// block, a (gridDim.x, 2, D) partial slab.
-template <typename T, bool HAS_MASK, bool HAS_NORM>
+// HAS_ADD off: r_out is the op's x, d_r_out is not read and d_res is dx.
+// vec4 dw/db: the lane owns the same columns in every row, so they accumulate
+// in registers across the row loop (no atomics in it); one LDS combine per
+// block, then a (gridDim.x, 2, D) partial slab that the host sums.
+template <typename T, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
 __global__ void __launch_bounds__(256)
 dal_bwd_vec4(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
              const T* __restrict__ r_out, const float* __restrict__ w,
@@ -294,7 +304,7 @@ dal_bwd_vec4(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
   for (int64_t row = row0; row < n_rows; row += stride_rows) {
     const int64_t off = row * D + j0;
     float t[4] = {0.f, 0.f, 0.f, 0.f};
-    if (active) ld4(d_r_out + off, t);
+    if (HAS_ADD && active) ld4(d_r_out + off, t);
     if (HAS_NORM) {
       float g[4] = {0.f, 0.f, 0.f, 0.f}, xv[4] = {0.f, 0.f, 0.f, 0.f};
       if (active) {
@@ -317,7 +327,8 @@ dal_bwd_vec4(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
       if (active) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          t[i] += rs * (gw[i] - bsum - xh[i] * a);
+          const float dx = rs * (gw[i] - bsum - xh[i] * a);
+          t[i] = HAS_ADD ? t[i] + dx : dx;
           dwacc[i] += g[i] * xh[i];
           dbacc[i] += g[i];
         }
@@ -347,7 +358,7 @@ dal_bwd_vec4(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
   }
 }
 
-template <typename T, int MAX_PER_LANE, bool HAS_MASK, bool HAS_NORM>
+template <typename T, int MAX_PER_LANE, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
 __global__ void __launch_bounds__(256)
 dal_bwd_kernel(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
                const T* __restrict__ r_out, const float* __restrict__ w,
@@ -402,9 +413,10 @@ dal_bwd_kernel(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
       if (i * DR_WAVE >= D) break;
       const int j = lane + i * DR_WAVE;
       if (j < D) {
-        float t = ldf(d_r_out + base + j);
+        float t = HAS_ADD ? ldf(d_r_out + base + j) : 0.f;
         if (HAS_NORM) {
-          t += rs * (gy[i] - bsum - xh[i] * a);
+          const float dx = rs * (gy[i] - bsum - xh[i] * a);
+          t = HAS_ADD ? t + dx : dx;
           stf(d_res + base + j, t);
           const float g = ldf(d_normed + base + j);
           atomicAdd(&dw_s[j], g * xh[i]);
@@ -424,7 +436,7 @@ dal_bwd_kernel(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
 }
 
 // D > 1024: two passes over the row, nothing held per lane (see dal_fwd_stream)
-template <typename T, bool HAS_MASK, bool HAS_NORM>
+template <typename T, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
 __global__ void __launch_bounds__(256)
 dal_bwd_stream(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
                const T* __restrict__ r_out, const float* __restrict__ w,
@@ -463,11 +475,12 @@ dal_bwd_stream(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
       bsum = wave_sum(bsum) / D;
     }
     for (int j = lane; j < D; j += DR_WAVE) {
-      float t = ldf(d_r_out + base + j);
+      float t = HAS_ADD ? ldf(d_r_out + base + j) : 0.f;
       if (HAS_NORM) {
         const float g = ldf(d_normed + base + j);
         const float h = (ldf(r_out + base + j) - mu) * rs;
-        t += rs * (g * w[j] - bsum - h * a);
+        const float dx = rs * (g * w[j] - bsum - h * a);
+        t = HAS_ADD ? t + dx : dx;
         stf(d_res + base + j, t);
         atomicAdd(&dw_s[j], g * h);
         atomicAdd(&db_s[j], g);
@@ -485,7 +498,7 @@ dal_bwd_stream(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
 }
 
 // ---------------------------------------------------------------- launchers
-template <typename T, bool HAS_MASK, bool HAS_NORM>
+template <typename T, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
 static void dal_fwd_launch_t(const void* branch, const void* residual, const float* w,
                              const float* b, const int64_t* seed, uint32_t thr,
                              float scale, void* r_out, void* normed, float* mean,
@@ -500,18 +513,18 @@ static void dal_fwd_launch_t(const void* branch, const void* residual, const flo
                      (const T*)branch, (const T*)residual, w, b, seed, thr,    \
                      scale, (T*)r_out, (T*)normed, mean, rstd, n_rows, D, eps)
   if ((D % 4) == 0 && D <= 4 * DR_WAVE) {
-    DR_DAL_FWD(dal_fwd_vec4<T, HAS_MASK, HAS_NORM>);
+    DR_DAL_FWD(dal_fwd_vec4<T, HAS_ADD, HAS_MASK, HAS_NORM>);
   } else if (D <= 256) {
-    DR_DAL_FWD(dal_fwd_kernel<T, 4, HAS_MASK, HAS_NORM>);
+    DR_DAL_FWD(dal_fwd_kernel<T, 4, HAS_ADD, HAS_MASK, HAS_NORM>);
   } else if (D <= 1024) {
-    DR_DAL_FWD(dal_fwd_kernel<T, 16, HAS_MASK, HAS_NORM>);
+    DR_DAL_FWD(dal_fwd_kernel<T, 16, HAS_ADD, HAS_MASK, HAS_NORM>);
   } else {
-    DR_DAL_FWD(dal_fwd_stream<T, HAS_MASK, HAS_NORM>);
+    DR_DAL_FWD(dal_fwd_stream<T, HAS_ADD, HAS_MASK, HAS_NORM>);
   }
 #undef DR_DAL_FWD
 }
 
-template <typename T, bool HAS_MASK, bool HAS_NORM>
+template <typename T, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
 static void dal_bwd_launch_t(const void* d_normed, const void* d_r_out,
                              const void* r_out, const float* w, const float* mean,
                              const float* rstd, const int64_t* seed, uint32_t thr,
@@ -526,13 +539,13 @@ static void dal_bwd_launch_t(const void* d_normed, const void* d_r_out,
                      mean, rstd, seed, thr, scale, (T*)d_res, (T*)d_branch,    \
                      dwdb_part, n_rows, D)
   if ((D % 4) == 0 && D <= 4 * DR_WAVE) {
-    DR_DAL_BWD(dal_bwd_vec4<T, HAS_MASK, HAS_NORM>);
+    DR_DAL_BWD(dal_bwd_vec4<T, HAS_ADD, HAS_MASK, HAS_NORM>);
   } else if (D <= 256) {
-    DR_DAL_BWD(dal_bwd_kernel<T, 4, HAS_MASK, HAS_NORM>);
+    DR_DAL_BWD(dal_bwd_kernel<T, 4, HAS_ADD, HAS_MASK, HAS_NORM>);
   } else if (D <= 1024) {
-    DR_DAL_BWD(dal_bwd_kernel<T, 16, HAS_MASK, HAS_NORM>);
+    DR_DAL_BWD(dal_bwd_kernel<T, 16, HAS_ADD, HAS_MASK, HAS_NORM>);
   } else {
-    DR_DAL_BWD(dal_bwd_stream<T, HAS_MASK, HAS_NORM>);
+    DR_DAL_BWD(dal_bwd_stream<T, HAS_ADD, HAS_MASK, HAS_NORM>);
   }
 #undef DR_DAL_BWD
 }
@@ -540,7 +553,9 @@ static void dal_bwd_launch_t(const void* d_normed, const void* d_r_out,
 }  // namespace dr
 
 // ---- C ABI launchers (called from bindings.cpp) ----
-// has_mask: seed != nullptr; has_norm: w != nullptr.
+// has_mask: seed != nullptr; has_norm: w != nullptr.  branch == nullptr
+// (forward) / d_r_out == nullptr (backward) is plain LayerNorm, which takes
+// no seed and needs w: bindings.cpp checks both before it calls.
 extern "C" {
 
 void dr_dropout_add_ln_fwd(const void* branch, const void* residual, const float* w,
@@ -548,16 +563,18 @@ void dr_dropout_add_ln_fwd(const void* branch, const void* residual, const float
                            float scale, void* r_out, void* normed, float* mean,
                            float* rstd, int64_t n_rows, int D, float eps,
                            int is_bf16, hipStream_t stream) {
-  const bool m = seed != nullptr, n = w != nullptr;
-#define DR_DAL_GO(T, M, N)                                                     \
-  dr::dal_fwd_launch_t<T, M, N>(branch, residual, w, b, seed, thr, scale,      \
-                                r_out, normed, mean, rstd, n_rows, D, eps, stream)
+  const bool a = branch != nullptr, m = seed != nullptr, n = w != nullptr;
+#define DR_DAL_GO(T, A, M, N)                                                  \
+  dr::dal_fwd_launch_t<T, A, M, N>(branch, residual, w, b, seed, thr, scale,   \
+                                   r_out, normed, mean, rstd, n_rows, D, eps,  \
+                                   stream)
 #define DR_DAL_T(T)                                                            \
   do {                                                                         \
-    if (m && n) DR_DAL_GO(T, true, true);                                      \
-    else if (m) DR_DAL_GO(T, true, false);                                     \
-    else if (n) DR_DAL_GO(T, false, true);                                     \
-    else DR_DAL_GO(T, false, false);                                           \
+    if (!a) DR_DAL_GO(T, false, false, true);                                  \
+    else if (m && n) DR_DAL_GO(T, true, true, true);                           \
+    else if (m) DR_DAL_GO(T, true, true, false);                               \
+    else if (n) DR_DAL_GO(T, true, false, true);                               \
+    else DR_DAL_GO(T, true, false, false);                                     \
   } while (0)
   if (is_bf16) DR_DAL_T(uint16_t); else DR_DAL_T(float);
 #undef DR_DAL_T
@@ -572,16 +589,17 @@ void dr_dropout_add_ln_bwd(const void* d_normed, const void* d_r_out,
                            float scale, void* d_res, void* d_branch,
                            float* dwdb_part, int n_blocks, int64_t n_rows, int D,
                            int is_bf16, hipStream_t stream) {
-  const bool m = seed != nullptr, n = w != nullptr;
-#define DR_DAL_GO(T, M, N)                                                     \
-  dr::dal_bwd_launch_t<T, M, N>(d_normed, d_r_out, r_out, w, mean, rstd, seed, \
-                                thr, scale, d_res, d_branch, dwdb_part,        \
-                                n_blocks, n_rows, D, stream)
+  const bool a = d_r_out != nullptr, m = seed != nullptr, n = w != nullptr;
+#define DR_DAL_GO(T, A, M, N)                                                  \
+  dr::dal_bwd_launch_t<T, A, M, N>(d_normed, d_r_out, r_out, w, mean, rstd,    \
+                                   seed, thr, scale, d_res, d_branch,          \
+                                   dwdb_part, n_blocks, n_rows, D, stream)
 #define DR_DAL_T(T)                                                            \
   do {                                                                         \
-    if (m && n) DR_DAL_GO(T, true, true);                                      \
-    else if (m) DR_DAL_GO(T, true, false);                                     \
-    else if (n) DR_DAL_GO(T, false, true);                                     \
+    if (!a) DR_DAL_GO(T, false, false, true);                                  \
+    else if (m && n) DR_DAL_GO(T, true, true, true);                           \
+    else if (m) DR_DAL_GO(T, true, true, false);                               \
+    else if (n) DR_DAL_GO(T, true, false, true);                               \
   } while (0)
   if (is_bf16) DR_DAL_T(uint16_t); else DR_DAL_T(float);
 #undef DR_DAL_T

@@ -1,9 +1,10 @@
 """LayerNorm (fwd/bwd) — hand-written HIP kernel on GPU.
 
-Absent in the reference model; required by the new MHA traffic encoder
-(SURVEY.md section 2.6 row "LayerNorm").  Memory-bound: the kernel does one
-vectorized read (short4/float4), wave-level Welford-free two-pass-in-registers
-reduction, and a fused affine, targeting the HBM roofline.
+The kernels are the residual-norm ones (csrc/residual_norm.hip) with the add
+compiled out: ``layer_norm(x)`` is ``dropout_add_layer_norm`` with no branch,
+no ``r_out`` copy and no gradient arriving through ``r_out``.  Memory-bound:
+one wave per row, vectorized IO, two-pass statistics over wave shuffles and
+a fused affine; docs/KERNELS.md has the tiers.  Backward needs D <= 8192.
 """
 
 from __future__ import annotations
@@ -23,7 +24,8 @@ class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
         ext = require_native("layer_norm")
-        y, mean, rstd = ext.layer_norm_forward(x, weight, bias, float(eps))
+        _, y, mean, rstd = ext.dropout_add_ln_forward(
+            None, x, weight, bias, None, 0.0, float(eps))
         ctx.save_for_backward(x, weight, mean, rstd)
         return y
 
@@ -31,7 +33,8 @@ class _LayerNorm(torch.autograd.Function):
     def backward(ctx, grad_y):
         ext = require_native("layer_norm")
         x, weight, mean, rstd = ctx.saved_tensors
-        dx, dw, db = ext.layer_norm_backward(grad_y.contiguous(), x, weight, mean, rstd)
+        dx, _, dw, db = ext.dropout_add_ln_backward(
+            grad_y.contiguous(), None, x, weight, mean, rstd, None, 0.0)
         return dx, dw, db, None
 
 

@@ -19,9 +19,8 @@ CSRC = os.path.join(ROOT, "deeprest_amd", "csrc")
 
 sources = [
     os.path.join(CSRC, f)
-    for f in ["bindings.cpp", "featurize.cpp", "layernorm.hip", "residual_norm.hip",
-              "pinball.hip", "adam.hip", "gru.hip", "attention.hip",
-              "sanity.hip"]
+    for f in ["bindings.cpp", "featurize.cpp", "residual_norm.hip", "pinball.hip",
+              "adam.hip", "gru.hip", "attention.hip", "sanity.hip"]
 ]
 
 setup(

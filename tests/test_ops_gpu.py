@@ -26,8 +26,17 @@ def dev():
 
 
 # ------------------------------------------------------------------ layernorm
+# strided tier below 256 with D % 4 != 0; streaming tier; one past 64 values
+# per lane; grid-stride loop past 2048 blocks x 4 waves.  These get the
+# upstream gradient rounded to the IO dtype for kernel AND reference: over
+# 8200 bf16 rows the rounding of g itself adds ~sqrt(8200) * 2^-9 = 0.18 per
+# unit of gradient to dw, which is the test's error and not the kernel's.
+_LN_ROUNDED_G_SHAPES = [(3, 70), (3, 1090), (2, 4100), (8200, 64)]
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("shape", [(8, 16, 256), (3, 7, 192), (1, 1, 64), (5, 1024)])
+@pytest.mark.parametrize("shape", [(8, 16, 256), (3, 7, 192), (1, 1, 64), (5, 1024)]
+                         + _LN_ROUNDED_G_SHAPES)
 def test_layernorm_fwd_bwd(dev, dtype, shape):
     from deeprest_amd.ops import layer_norm, reference_layer_norm
 
@@ -48,12 +57,31 @@ def test_layernorm_fwd_bwd(dev, dtype, shape):
     torch.testing.assert_close(y.float(), y_ref, **tol)
 
     g = torch.randn_like(y_ref)
+    if shape in _LN_ROUNDED_G_SHAPES:
+        g = g.to(dtype).float()
     y.backward(g.to(dtype))
     y_ref.backward(g)
     torch.testing.assert_close(x_t.grad.float(), x_ref.grad, rtol=5e-2 if dtype == torch.bfloat16 else 1e-4,
                                atol=5e-2 if dtype == torch.bfloat16 else 1e-4)
     torch.testing.assert_close(w_t.grad, w_ref.grad, rtol=5e-2, atol=5e-2)
     torch.testing.assert_close(b_t.grad, b_ref.grad, rtol=5e-2, atol=5e-2)
+
+
+def test_layernorm_backward_rejects_wide_rows(dev):
+    """dw/db partials take 2 * D floats of LDS per block: D > 8192 must raise
+    before any launch, not return an unwritten dx."""
+    from deeprest_amd.ops import layer_norm
+
+    D = 8200
+    x = torch.randn(1, D, device=dev, requires_grad=True)
+    w = torch.ones(D, device=dev, requires_grad=True)
+    b = torch.zeros(D, device=dev, requires_grad=True)
+    y = layer_norm(x, w, b)
+    torch.testing.assert_close(y, torch.nn.functional.layer_norm(x, (D,), w, b),
+                               rtol=2e-5, atol=2e-5)
+    with pytest.raises(RuntimeError, match="8192"):
+        y.sum().backward()
+    assert x.grad is None and w.grad is None and b.grad is None
 
 
 # -------------------------------------------------------------------- pinball

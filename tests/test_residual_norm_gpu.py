@@ -162,6 +162,38 @@ def test_dropout_add_fwd_bwd(dev, shape, p, dtype):
     torch.testing.assert_close(re_t.grad.float(), re_ref.grad, **_grad_tol(dtype))
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", [(7, 192), (3, 70), (3, 1090)])
+def test_layer_norm_equals_fused_with_zero_branch(dev, shape, dtype):
+    """Plain layer_norm is the same kernels with the add compiled out.  Adding
+    an exact zero and rounding a value already in the IO dtype change no bits,
+    so y and dx must be EQUAL; a difference means the add-off path reads or
+    writes the wrong thing.  dw/db go through LDS float atomics from four
+    waves, whose order is not fixed even between two runs of the same code."""
+    from deeprest_amd.ops import dropout_add_layer_norm, layer_norm
+
+    torch.manual_seed(2)
+    D = shape[-1]
+    x = (torch.randn(*shape, device=dev) * 2 + 0.5).to(dtype)
+    w = torch.randn(D, device=dev) * 0.5 + 1.0
+    b = torch.randn(D, device=dev) * 0.1
+    g = torch.randn(*shape, device=dev).to(dtype)
+
+    x_p, w_p, b_p = (t.clone().requires_grad_(True) for t in (x, w, b))
+    y = layer_norm(x_p, w_p, b_p)
+    y.backward(g)
+
+    x_f, w_f, b_f = (t.clone().requires_grad_(True) for t in (x, w, b))
+    r_out, normed = dropout_add_layer_norm(torch.zeros_like(x), x_f, w_f, b_f)
+    normed.backward(g)
+
+    assert torch.equal(r_out, x)
+    assert torch.equal(y, normed)
+    assert torch.equal(x_p.grad, x_f.grad)
+    torch.testing.assert_close(w_p.grad, w_f.grad, rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(b_p.grad, b_f.grad, rtol=1e-5, atol=1e-6)
+
+
 def test_mixed_dtypes_promote_like_eager(dev):
     from deeprest_amd.ops import dropout_add
 
