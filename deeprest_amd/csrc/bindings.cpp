@@ -49,21 +49,25 @@ void dr_fused_adam_dev(const int64_t* meta, int nt, int64_t total,
 // the dr_gru_* entries return the HIP error of their set-up or launches, 0 on
 // success (gru_launch_check below)
 int dr_gru_fwd_fuses_heads(int B, int C);
+// `images`: dr_gru_operand_images_bytes(C, is_bf16) bytes of device memory in
+// which the entries build the pi-ordered gamma / beta / b_hh images that their
+// streaming kernel variants read (gamma / beta / b_hh stay natural-layout)
+int64_t dr_gru_operand_images_bytes(int C, int is_bf16);
 int dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
                const void* w_hh, const float* b_hh, const void* h0, void* h_all,
                void* saves, const void* wh_fwd, void* out, int O, int B, int TT,
-               int C, int reverse, int save, int fp8, int is_bf16,
+               int C, int reverse, int save, int fp8, int is_bf16, void* images,
                hipStream_t stream);
 int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
                   const void* w_hh, const float* b_hh, const void* h0,
                   const void* wh_fwd, void* out, void* h_last, int B, int TT,
                   int C, int O, int reverse, int fp8, int is_bf16,
-                  const int* lens, hipStream_t stream);
+                  const int* lens, void* images, hipStream_t stream);
 int dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
                const void* w_fwd, const void* xg, const void* gamma,
                const void* beta, const float* b_hh, const void* h0,
                const void* h_all, const void* saves, void* dpre, float* dh0,
-               int B, int TT, int C, int reverse, int is_bf16,
+               int B, int TT, int C, int reverse, int is_bf16, void* images,
                hipStream_t stream);
 int dr_gru_reduce_fused_max_c();
 int dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
@@ -477,6 +481,15 @@ static void check_wh_fwd(const at::Tensor& wh_fwd, int64_t O, int H) {
               "wh_fwd must be the (32, H) bf16 head weight image");
 }
 
+// Scratch for the chain kernels' pi-ordered operand images, from the torch
+// allocator (stream-ordered, no host sync: graph-capturable).  The launcher
+// fills it on the current stream; it lives until the call's kernels are
+// queued, and the caching allocator does not hand it to another stream.
+static at::Tensor gru_operand_images(const at::Tensor& gamma, int C) {
+  return at::empty({dr_gru_operand_images_bytes(C, is_bf16(gamma))},
+                   gamma.options().dtype(at::kByte));
+}
+
 // Whether gru_seq_forward at these sizes takes wh_fwd and runs the head
 // projection inside the kernel; callers ask here, the launcher decides.
 bool gru_fwd_fuses_heads(int64_t B, int64_t C, bool save) {
@@ -515,6 +528,7 @@ std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
   auto out = heads ? at::empty({B, TT, C, O}, xg.options())
                    : at::empty({0}, xg.options());
   auto w_gemm = gru_w_gemm(w_hh);
+  auto images = gru_operand_images(gamma, C);
   gru_launch_check(
       dr_gru_fwd(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                  w_gemm.data_ptr(), b_hh.data_ptr<float>(), h0.data_ptr(),
@@ -522,7 +536,7 @@ std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
                  heads ? wh_fwd->data_ptr() : nullptr,
                  heads ? out.data_ptr() : nullptr, heads ? (int)O : 0, B, TT, C,
                  reverse ? 1 : 0, save ? 1 : 0, fp8 ? 1 : 0, is_bf16(xg),
-                 cur_stream()),
+                 images.data_ptr(), cur_stream()),
       "gru forward");
   if (!heads) return {h_all, saves};
   return {h_all, saves, out};
@@ -554,12 +568,13 @@ std::vector<at::Tensor> gru_seq_decode(at::Tensor xg, at::Tensor w_hh,
                   : at::empty({B, TT, C, O}, xg.options());
   auto h_last = at::empty({B, C, H}, xg.options());
   auto w_gemm = gru_w_gemm(w_hh);
+  auto images = gru_operand_images(gamma, C);
   gru_launch_check(
       dr_gru_decode(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                     w_gemm.data_ptr(), b_hh.data_ptr<float>(), h0.data_ptr(),
                     wh_fwd.data_ptr(), out.data_ptr(), h_last.data_ptr(), B, TT,
                     C, (int)O, reverse ? 1 : 0, fp8 ? 1 : 0, is_bf16(xg), lens,
-                    cur_stream()),
+                    images.data_ptr(), cur_stream()),
       "gru decode");
   return {out, h_last};
 }
@@ -619,13 +634,15 @@ static std::vector<at::Tensor> gru_backward_impl(
   TORCH_CHECK(grad_h.is_contiguous() && h_all.is_contiguous() && saves.is_contiguous());
   auto dpre = at::empty({B, TT, C, 4 * H}, grad_h.options());
   auto dh0 = at::empty({B, C, H}, grad_h.options().dtype(at::kFloat));
+  auto images = gru_operand_images(gamma, C);
   gru_launch_check(
       dr_gru_bwd(grad_h.data_ptr(), wh_img ? wh_img->data_ptr() : nullptr, O,
                  w_img.data_ptr(), w_fwd.data_ptr(), xg.data_ptr(),
                  gamma.data_ptr(), beta.data_ptr(), b_hh.data_ptr<float>(),
                  h0.data_ptr(), h_all.data_ptr(), saves.data_ptr(),
                  dpre.data_ptr(), dh0.data_ptr<float>(), B, TT, C,
-                 reverse ? 1 : 0, dt == at::kBFloat16, cur_stream()),
+                 reverse ? 1 : 0, dt == at::kBFloat16, images.data_ptr(),
+                 cur_stream()),
       "gru backward");
   return {dpre, dh0};
 }

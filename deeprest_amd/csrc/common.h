@@ -87,16 +87,22 @@ __device__ __forceinline__ float group16_max(float v) {
   return v;
 }
 
+// Gate nonlinearities on v_exp_f32 + v_rcp_f32 (1 ulp each), 4-5 instructions.
+// __fdividef is a full IEEE division on this target without -ffast-math
+// (2 v_div_scale + v_rcp + 6 FMA/mul + v_div_fmas + v_div_fixup); the
+// hardware reciprocal moves a result in its last fp32 bit at most a few ulp,
+// far below the bf16 rounding every consumer applies.
 __device__ __forceinline__ float sigmoidf_(float x) {
-  // fast path: v_exp + fast divide; exp(-x) -> inf for x << 0 gives 1/inf = 0
-  return __fdividef(1.0f, 1.0f + __expf(-x));
+  // exp(-x) -> inf for x << 0 gives rcp(inf) = 0
+  return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
 }
 
 __device__ __forceinline__ float tanhf_(float x) {
-  // clamp so exp never overflows into inf/inf = NaN; tanh(+-15) == +-1 in f32
+  // clamp so exp never overflows into inf * 0 = NaN; tanh(+-15) is +-1 in
+  // f32, here to within the reciprocal's ulp
   float xc = fminf(fmaxf(x, -15.f), 15.f);
   float e = __expf(2.f * xc);
-  return __fdividef(e - 1.f, e + 1.f);
+  return (e - 1.f) * __builtin_amdgcn_rcpf(e + 1.f);
 }
 
 // ---- MFMA fragment types (gfx950) ----

@@ -149,6 +149,54 @@ __device__ __forceinline__ void ld8<float>(const float* src, float* v) {
   *reinterpret_cast<float4*>(v + 4) = *reinterpret_cast<const float4*>(src + 4);
 }
 
+// 8 IO values as loaded, bf16 (4 registers) or f32 (8), widened where used
+template <typename T> struct Raw8;
+template <> struct Raw8<uint16_t> { uint4 v; };
+template <> struct Raw8<float> { float4 a, b; };
+__device__ __forceinline__ void widen8(const Raw8<uint16_t>& p, float* v) {
+  const uint32_t w[4] = {p.v.x, p.v.y, p.v.z, p.v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = __uint_as_float(w[i] << 16);
+    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+  }
+}
+__device__ __forceinline__ void widen8(const Raw8<float>& p, float* v) {
+  v[0] = p.a.x; v[1] = p.a.y; v[2] = p.a.z; v[3] = p.a.w;
+  v[4] = p.b.x; v[5] = p.b.y; v[6] = p.b.z; v[7] = p.b.w;
+}
+// 8 values at a 32-bit BYTE offset from a kernel-argument pointer.  The base
+// stays a uniform global pointer and the offset one VGPR, so the load is a
+// global_load_dwordx4 with a scalar base; an opaque POINTER would lose its
+// address space and come out as flat loads behind 64-bit vector adds.
+template <typename T>
+__device__ __forceinline__ Raw8<T> ld_raw_at(const T* base, uint32_t byte_off);
+template <>
+__device__ __forceinline__ Raw8<uint16_t> ld_raw_at<uint16_t>(const uint16_t* base,
+                                                              uint32_t byte_off) {
+  return {*reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(base) + byte_off)};
+}
+template <>
+__device__ __forceinline__ Raw8<float> ld_raw_at<float>(const float* base,
+                                                        uint32_t byte_off) {
+  const char* p = reinterpret_cast<const char*>(base) + byte_off;
+  return {*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 16)};
+}
+// A product rounded on its own, whatever -ffp-contract allows around it
+// (__fmul_rn is a plain multiply here and gets contracted like one).
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+// A zero the optimizer cannot see through.  Added to the offset of a
+// t-invariant operand inside the time loop it keeps the loads in the loop
+// (hoisted they would take registers the streaming variants do not have).
+__device__ __forceinline__ uint32_t opaque_zero() {
+  uint32_t z = 0;
+  asm volatile("" : "+v"(z));
+  return z;
+}
+
 // store an 8-wide bf16 fragment to a T-typed tensor (bf16: one 16 B store)
 template <typename T>
 __device__ __forceinline__ void st_frag(T* dst, bf16x8 v);
@@ -226,14 +274,20 @@ __device__ __forceinline__ bf16x8 ld_frag<float>(const float* src) {
 // instead of holding them in 120 registers — gamma / beta rounded to bf16 on
 // the way, so the values are the ones the packed registers hold.  h_last is
 // each row's state after its own last valid step.
+// Whether a forward variant holds gamma / beta / b_hh in registers.  The
+// others stream them per step from the pi-ordered operand images (see
+// gru_operand_images_kernel), which their launcher builds first.
+template <bool FP8, int NSUB, bool VARLEN>
+constexpr bool fwd_gb_regs = (NSUB == 1) && !(VARLEN && FP8);
+
 template <typename T, bool SAVE, bool FP8 = false, int NSUB = 1, bool HEADS = false,
           bool VARLEN = false>
 __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     const T* __restrict__ xg,      // (B, TT, 3H)
-    const T* __restrict__ gamma,   // (C, 3H)
-    const T* __restrict__ beta,    // (C, 3H)
+    const T* __restrict__ gamma,   // (C, 3H); the streaming variants (!GB_REGS)
+    const T* __restrict__ beta,    // (C, 3H)  take the pi-ordered operand
     const uint16_t* __restrict__ w_gemm,  // (3H, H) bf16 GEMM weight image
-    const float* __restrict__ b_hh,  // (3H,)
+    const float* __restrict__ b_hh,  // (3H,)  images of these three instead
     const T* __restrict__ h0,      // (B, C, H)
     T* __restrict__ h_all,         // (B, TT, C, H)
     T* __restrict__ saves,         // (B, TT, C, 4H) pi layout (SAVE only)
@@ -255,7 +309,7 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
   char* Hl = smem + L::HM;
   char* XGl = smem + L::XG;
   // gamma/beta/b_hh in registers (NSUB == 1) or streamed per step
-  constexpr bool GB_REGS = (NSUB == 1) && !(VARLEN && FP8);
+  constexpr bool GB_REGS = fwd_gb_regs<FP8, NSUB, VARLEN>;
 
   const int tid = threadIdx.x;
   const int wv = tid / DR_WAVE;
@@ -318,13 +372,18 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
   // NSUB==1: gamma/beta packed as bf16 pairs in one u32 per (row, gate,
   // tile) — LDS caps this variant at 1 block/CU so the registers are free.
   // NSUB==2: two waves/SIMD need the registers back; gamma/beta/b_hh are
-  // L1/L2-resident and reload per step (opaque pointers in the epilogue).
+  // L1/L2-resident and reload per step from the pi-ordered images, where a
+  // lane's 8 values of one (row, gate) are one 16-byte load (f32: two).
   constexpr int GBN = GB_REGS ? 8 : 1;
   uint32_t gb[4][3][GBN];
   float bh[3][GBN];
-  int gb_off[4];
+  int gb_off[4];            // GB_REGS: element offset of the row's component
+  uint32_t gbi_off[4];      // streaming: byte offset of the lane's r slice
 #pragma unroll
-  for (int i = 0; i < 4; ++i) gb_off[i] = comp_of[i] * G3H;
+  for (int i = 0; i < 4; ++i) {
+    gb_off[i] = comp_of[i] * G3H;
+    gbi_off[i] = (uint32_t)(comp_of[i] * G3H + c_col * 8) * (uint32_t)sizeof(T);
+  }
   if constexpr (GB_REGS) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -442,6 +501,10 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     // VARLEN: row i is active at this step iff t_now < len_of[i]
     const int t_now = reverse ? (TT - 1 - step) : step;
     (void)t_now;
+    // opaque per step: keeps the streamed operand loads inside the loop
+    uint32_t zoff = 0;
+    if constexpr (!GB_REGS) zoff = opaque_zero();
+    (void)zoff;
     // A-fragments: this wave's 16 rows of the h tile, all 4 K-tiles
     bf16x8 afrag[KT];
     int64_t afrag8[KT];
@@ -454,8 +517,9 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     }
 
     // stage xg[., t, :] into LDS in pi layout: the 8 loaded naturals land at
-    // positions pi_0 + 8e (16 B stride), so the epilogue reads each (row,
-    // gate) slice as ONE ds_read_b128 instead of 8 scalar reads.
+    // positions pi_0 + 8e (16 B stride), so a (row, gate) slice is 16
+    // contiguous bytes: ONE ds_read_b128 in the streaming epilogue (the
+    // register-holding tiles still read it as 8 ds_read_u16, see there).
 #pragma unroll
     for (int u = 0; u < MAXCH; ++u) {        // compile-time index (rule 20)
       if (u < n_stage) {
@@ -473,6 +537,11 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     wave_lds_fence();
 
     // ---- MFMA: hh = h_tile @ W^T -> (64, 384), this wave's 16 rows ----
+    // One tile at a time, each MFMA behind its own fragment read.  Advancing
+    // several tiles together with the reads ahead of the MFMAs (groups of 2
+    // and 4, with and without a double buffer) put every HEADS variant of the
+    // 8-wave tile 4 to 12 registers into scratch; see
+    // profiles/r12_gru_epilogue.md.
     f32x4 acc[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -493,83 +562,170 @@ __global__ __launch_bounds__(THREADS * NSUB) void gru_fwd_kernel(
     }
 
     // ---- fused gate epilogue (vectorized pi-layout saves) ----
-    const T* gm_v = gamma;
-    const T* bt_v = beta;
-    const float* bh_v = b_hh;
-    if constexpr (!GB_REGS) asm volatile("" : "+v"(gm_v), "+v"(bt_v), "+v"(bh_v));
+    if constexpr (GB_REGS) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const T* grow = gm_v + gb_off[i];
-      const T* brow = bt_v + gb_off[i];
-      float fr[8], fz[8], fn[8];
-      bool active = true;
-      if constexpr (VARLEN) active = t_now < len_of[i];
+      for (int i = 0; i < 4; ++i) {
+        float fr[8], fz[8];
+        bool active = true;
+        if constexpr (VARLEN) active = t_now < len_of[i];
 #pragma unroll
-      for (int nt = 0; nt < 8; ++nt) {
-        // pi layout: per-gate values sit at CONSECUTIVE LDS addresses over
-        // nt, so these scalar reads coalesce/merge cheaply
-        float xr = bf2f(xg_rows[i][nt]);
-        float xz = bf2f(xg_rows[i][H + nt]);
-        float xn = bf2f(xg_rows[i][2 * H + nt]);
-        int col = nt * 16 + c_col;
-        float gmr, gmz, gmn, btr, btz, btn, bhr, bhz, bhn;
-        if constexpr (GB_REGS) {
-          gmr = bf2f((uint16_t)gb[i][0][nt]); btr = bf2f((uint16_t)(gb[i][0][nt] >> 16));
-          gmz = bf2f((uint16_t)gb[i][1][nt]); btz = bf2f((uint16_t)(gb[i][1][nt] >> 16));
-          gmn = bf2f((uint16_t)gb[i][2][nt]); btn = bf2f((uint16_t)(gb[i][2][nt] >> 16));
-          bhr = bh[0][nt]; bhz = bh[1][nt]; bhn = bh[2][nt];
-        } else if constexpr (NSUB == 1) {
-          // streamed twin of the packed registers: same bf16-rounded values
-          gmr = bf2f(f2bf(ldf(grow + col))); btr = bf2f(f2bf(ldf(brow + col)));
-          gmz = bf2f(f2bf(ldf(grow + H + col)));
-          btz = bf2f(f2bf(ldf(brow + H + col)));
-          gmn = bf2f(f2bf(ldf(grow + 2 * H + col)));
-          btn = bf2f(f2bf(ldf(brow + 2 * H + col)));
-          bhr = bh_v[col]; bhz = bh_v[H + col]; bhn = bh_v[2 * H + col];
-        } else {
-          gmr = ldf(grow + col); btr = ldf(brow + col);
-          gmz = ldf(grow + H + col); btz = ldf(brow + H + col);
-          gmn = ldf(grow + 2 * H + col); btn = ldf(brow + 2 * H + col);
-          bhr = bh_v[col]; bhz = bh_v[H + col]; bhn = bh_v[2 * H + col];
+        for (int nt = 0; nt < 8; ++nt) {
+          // pi layout: the 8 values of a gate are 16 consecutive LDS bytes.
+          // Read one by one here (8 ds_read_u16 per gate): the 16-byte read
+          // of the streaming branch put these register-holding tiles into
+          // scratch.
+          float xr = bf2f(xg_rows[i][nt]);
+          float xz = bf2f(xg_rows[i][H + nt]);
+          float xn = bf2f(xg_rows[i][2 * H + nt]);
+          int col = nt * 16 + c_col;
+          float gmr = bf2f((uint16_t)gb[i][0][nt]), btr = bf2f((uint16_t)(gb[i][0][nt] >> 16));
+          float gmz = bf2f((uint16_t)gb[i][1][nt]), btz = bf2f((uint16_t)(gb[i][1][nt] >> 16));
+          float gmn = bf2f((uint16_t)gb[i][2][nt]), btn = bf2f((uint16_t)(gb[i][2][nt] >> 16));
+          float bhr = bh[0][nt], bhz = bh[1][nt], bhn = bh[2][nt];
+          float g_r = xr * gmr + btr;
+          float g_z = xz * gmz + btz;
+          float g_n = xn * gmn + btn;
+          float rp = sigmoidf_(acc[nt][i] + bhr + g_r);
+          float zp = sigmoidf_(acc[nt + 8][i] + bhz + g_z);
+          float hn = acc[nt + 16][i] + bhn;
+          float nn = tanhf_(g_n + rp * hn);
+          float hnew = (1.f - zp) * nn + zp * h[i][nt];
+          if constexpr (VARLEN) hnew = active ? hnew : h[i][nt];
+          h[i][nt] = hnew;
+          if constexpr (FP8)
+            *reinterpret_cast<uint8_t*>(Hl + swz8(row_of[i], col)) = f2fp8(hnew);
+          else
+            *reinterpret_cast<uint16_t*>(Hl + swz(row_of[i], col)) = f2bf(hnew);
+          fr[nt] = rp; fz[nt] = zp;
         }
-        float g_r, g_z, g_n;
-        if constexpr (!GB_REGS && NSUB == 1) {
-          // Pin what -ffp-contract leaves to the compiler, so that this
-          // variant computes bit for bit what its register-held twin does:
-          // there the r and z products are rounded before beta is added
-          // (they pair up with acc + b_hh into packed adds) and only the n
-          // gate is contracted into an FMA; with streamed operands all three
-          // came out as rounded packed multiplies (1 ulp apart in fp32 IO).
-          g_r = __fmul_rn(xr, gmr) + btr;
-          g_z = __fmul_rn(xz, gmz) + btz;
-          g_n = __builtin_fmaf(xn, gmn, btn);
-        } else {
-          g_r = xr * gmr + btr;
-          g_z = xz * gmz + btz;
-          g_n = xn * gmn + btn;
+        if (SAVE && live[i]) {
+          // only r and z are saved (2H); the backward recomputes n and hh_n
+          // (an extra H x H GEMM there is cheaper than 2H of HBM both ways)
+          T* sv = saves + (int64_t)(bc[i] + bc_toff) * (2 * H) + c_col * 8;
+          st8(sv, fr);
+          st8(sv + H, fz);
         }
-        float rp = sigmoidf_(acc[nt][i] + bhr + g_r);
-        float zp = sigmoidf_(acc[nt + 8][i] + bhz + g_z);
-        float hn = acc[nt + 16][i] + bhn;
-        float nn = tanhf_(g_n + rp * hn);
-        float hnew = (1.f - zp) * nn + zp * h[i][nt];
-        if constexpr (VARLEN) hnew = active ? hnew : h[i][nt];
-        h[i][nt] = hnew;
-        if constexpr (FP8)
-          *reinterpret_cast<uint8_t*>(Hl + swz8(row_of[i], col)) = f2fp8(hnew);
-        else
-          *reinterpret_cast<uint16_t*>(Hl + swz(row_of[i], col)) = f2bf(hnew);
-        fr[nt] = rp; fz[nt] = zp; fn[nt] = nn; (void)fn;
+        // fence: stop the scheduler interleaving all 4 rows' live ranges
+        __builtin_amdgcn_sched_barrier(0);
       }
-      if (SAVE && live[i]) {
-        // only r and z are saved (2H); the backward recomputes n and hh_n
-        // (an extra H x H GEMM there is cheaper than 2H of HBM both ways)
-        T* sv = saves + (int64_t)(bc[i] + bc_toff) * (2 * H) + c_col * 8;
-        st8(sv, fr);
-        st8(sv + H, fz);
+    } else {
+      // Streaming variants.  The epilogue is 12 stages, (row, gate) in the
+      // order r, z, n.  A stage's operands are three 16-byte reads: gamma and
+      // beta from the pi images (global, f32: two each) and x_gates from the
+      // wave's pi-ordered slot (one ds_read_b128).  The global ones are
+      // issued one stage AHEAD (bf16 IO), so their latency passes under the
+      // previous stage's eight sigmoids / tanhs; the LDS read stays at the
+      // head of its own stage (4 more registers in flight spill).  The
+      // scheduling barriers keep that order and keep the stages' live ranges
+      // apart.
+      struct Stage { Raw8<T> gm, bt; };
+      auto issue = [&](int i, int g) {
+        const uint32_t off = gbi_off[i] + zoff + (uint32_t)(g * H * sizeof(T));
+        return Stage{ld_raw_at<T>(gamma, off), ld_raw_at<T>(beta, off)};
+      };
+      // gate pre-activation x * gamma + beta of one stage, 8 N-tiles
+      auto film = [&](const Stage& st, int i, int g, float* out) {
+        float xv[8], gmv[8], btv[8];
+        widen8(Raw8<uint16_t>{*reinterpret_cast<const uint4*>(xg_rows[i] + g * H)}, xv);
+        widen8(st.gm, gmv);
+        widen8(st.bt, btv);
+#pragma unroll
+        for (int nt = 0; nt < 8; ++nt) {
+          if constexpr (NSUB == 1) {
+            // Streamed twin of the packed registers (the lengths FP8 tile):
+            // the same bf16-rounded values, and what -ffp-contract leaves to
+            // the compiler pinned to what the register-held kernel does —
+            // there the r and z products are rounded before beta is added
+            // and only the n gate is contracted into an FMA.
+            float gm = gmv[nt], bt = btv[nt];
+            if constexpr (sizeof(T) == 4) { gm = bf2f(f2bf(gm)); bt = bf2f(f2bf(bt)); }
+            out[nt] = g < 2 ? mul_rounded(xv[nt], gm) + bt : __builtin_fmaf(xv[nt], gm, bt);
+          } else {
+            // the 8-wave tile contracts all three into FMAs, as it always has
+            out[nt] = __builtin_fmaf(xv[nt], gmv[nt], btv[nt]);
+          }
+        }
+      };
+      // b_hh joins the accumulators once per step: six 16-byte loads serve
+      // all four rows
+#pragma unroll
+      for (int g = 0; g < 3; ++g) {
+        float bv[8];
+        widen8(ld_raw_at<float>(b_hh, (uint32_t)(g * H + c_col * 8) * 4u + zoff), bv);
+#pragma unroll
+        for (int nt = 0; nt < 8; ++nt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc[g * 8 + nt][i] += bv[nt];
       }
-      // fence: stop the scheduler interleaving all 4 rows' live ranges
+      // Mirror write addresses, all 32 from ONE register: row i of the lane
+      // and N-tile nt only flip bits of the swizzled block index of (row 0,
+      // tile 0) — one XOR with a constant — and the row's byte offset goes
+      // into the instruction's offset field.  Opaque per step, or the 32
+      // addresses come back as loop-invariant registers.
+      constexpr int MIRROR_ROW_SHIFT = FP8 ? 3 : 4;    // 8 / 16 B blocks
+      constexpr int MIRROR_NT_SHIFT = MIRROR_ROW_SHIFT + 1;
+      constexpr int MIRROR_ROW_BYTES = FP8 ? 128 : 256;
+      const int hm0 = (FP8 ? swz8(row_of[0], c_col) : swz(row_of[0], c_col)) + (int)zoff;
+      // f32 IO: a stage is 20 registers, and a second one in flight spills;
+      // those tiles issue each stage's loads at its own head.
+      constexpr bool AHEAD = sizeof(T) == 2;
+      Stage cur, nxt;
+      if constexpr (AHEAD) cur = issue(0, 0);
       __builtin_amdgcn_sched_barrier(0);
+      float fr[8], fz[8];
+#pragma unroll
+      for (int s = 0; s < 12; ++s) {
+        const int i = s / 3, g = s % 3;
+        if constexpr (AHEAD) {
+          if (s + 1 < 12) nxt = issue((s + 1) / 3, (s + 1) % 3);
+        } else {
+          cur = issue(i, g);
+        }
+        float pre[8];
+        film(cur, i, g, pre);
+        if (g == 0) {
+#pragma unroll
+          for (int nt = 0; nt < 8; ++nt) fr[nt] = sigmoidf_(acc[nt][i] + pre[nt]);
+        } else if (g == 1) {
+#pragma unroll
+          for (int nt = 0; nt < 8; ++nt) fz[nt] = sigmoidf_(acc[nt + 8][i] + pre[nt]);
+        } else {
+          bool active = true;
+          if constexpr (VARLEN) active = t_now < len_of[i];
+#pragma unroll
+          for (int nt = 0; nt < 8; ++nt) {
+            const float hn = acc[nt + 16][i];
+            const float rp = fr[nt], zp = fz[nt];
+            float nn = tanhf_(pre[nt] + rp * hn);
+            // the blend, pinned like the gate sums above: the 8-wave tile
+            // contracts z * h into the sum, the register-held kernels (and
+            // so their streamed twin) round both products first
+            float hnew;
+            if constexpr (NSUB == 1)
+              hnew = mul_rounded(1.f - zp, nn) + mul_rounded(zp, h[i][nt]);
+            else
+              hnew = __builtin_fmaf(zp, h[i][nt], mul_rounded(1.f - zp, nn));
+            if constexpr (VARLEN) hnew = active ? hnew : h[i][nt];
+            h[i][nt] = hnew;
+            // XOR, not OR: row bit 1 and N-tile bit 0 meet in the same bit
+            char* hm_p = Hl + (hm0 ^ ((i << MIRROR_ROW_SHIFT) ^ (nt << MIRROR_NT_SHIFT))) +
+                         i * MIRROR_ROW_BYTES;
+            if constexpr (FP8)
+              *reinterpret_cast<uint8_t*>(hm_p) = f2fp8(hnew);
+            else
+              *reinterpret_cast<uint16_t*>(hm_p) = f2bf(hnew);
+          }
+          if (SAVE && live[i]) {
+            // only r and z are saved (2H); the backward recomputes n and hh_n
+            // (an extra H x H GEMM there is cheaper than 2H of HBM both ways)
+            T* sv = saves + (int64_t)(bc[i] + bc_toff) * (2 * H) + c_col * 8;
+            st8(sv, fr);
+            st8(sv + H, fz);
+          }
+        }
+        if constexpr (AHEAD) cur = nxt;
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
     // the mirror rows written above are read below and at the top of the next
     // step by other lanes of this wave; the next step's slot writes stay
@@ -686,9 +842,9 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
     const uint16_t* __restrict__ w_img,  // (H, 384) bf16: w_img[k][m] = W[natJ(m)][k]
     const uint16_t* __restrict__ w_fwd,  // (3H, H) bf16 natural layout
     const T* __restrict__ xg,       // (B, TT, 3H)
-    const T* __restrict__ gamma,    // (C, 3H)
-    const T* __restrict__ beta,     // (C, 3H)
-    const float* __restrict__ b_hh, // (3H,)
+    const T* __restrict__ gamma,    // (C, 3H) pi-ordered operand image
+    const T* __restrict__ beta,     // (C, 3H) pi-ordered operand image
+    const float* __restrict__ b_hh, // (3H,) natural order
     const T* __restrict__ h0,       // (B, C, H)
     const T* __restrict__ h_all,    // (B, TT, C, H)
     const T* __restrict__ saves,    // (B, TT, C, 2H) pi layout: r|z
@@ -857,9 +1013,7 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
       }
     }
 
-    const T* gm_v = gamma;
-    const T* bt_v = beta;
-    asm volatile("" : "+v"(gm_v), "+v"(bt_v));
+    const uint32_t zoff = opaque_zero();   // keeps the FiLM loads in the loop
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (!live[i]) continue;
@@ -875,15 +1029,24 @@ __global__ __launch_bounds__(NSUB * THREADS) void gru_bwd_kernel(
                              : (h_all + (bc + dirC) * H);
       const T* gr_p = grad_h + bc * H;   // !FUSED only
       const T* xg_n = xg + xgb0[i] + xg_toff + 2 * H;
-      const T* gmn = gm_v + comp_of[i] * G3H + 2 * H;
-      const T* btn = bt_v + comp_of[i] * G3H + 2 * H;
+      // the n slices of the row's FiLM operands: one 16-byte load each
+      // from the pi images (f32: two)
+      float gmn[8], btn[8];
+      {
+        const uint32_t off =
+            (uint32_t)(comp_of[i] * G3H + 2 * H + c_col * 8) * (uint32_t)sizeof(T) + zoff;
+        const Raw8<T> gq = ld_raw_at<T>(gamma, off);
+        const Raw8<T> bq = ld_raw_at<T>(beta, off);
+        widen8(gq, gmn);
+        widen8(bq, btn);
+      }
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) {
         int col = nt * 16 + c_col;
         float hp = ldf(hsrc + col);
         // recompute the n gate: hh_n from the GEMM above, g_n from xg/FiLM
         float hn = hhn_acc[nt][i] + bhn[nt];
-        float g_n = ldf(xg_n + col) * ldf(gmn + col) + ldf(btn + col);
+        float g_n = ldf(xg_n + col) * gmn[nt] + btn[nt];
         float nn = tanhf_(g_n + rp[nt] * hn);
         float dht = dh_carry[nt][i];       // FUSED: head term already in
         if constexpr (!FUSED) dht += ldf(gr_p + col);
@@ -995,6 +1158,44 @@ __global__ void pi_permute_rows_kernel(const T* __restrict__ in,
     T* dst = out + r * G3H + g * H + cc * 8;
 #pragma unroll
     for (int e = 0; e < 8; ++e) dst[e] = src[e * 16];
+  }
+}
+
+// Pi-ordered images of the t-invariant operands the streaming chain kernels
+// re-read every step: gamma and beta (C, 3H) in the IO dtype, b_hh (3H) in
+// f32, in ONE buffer [gamma_pi | beta_pi | bhh_pi] that the caller allocates
+// (operand_images_bytes) and one launch fills.  The values are copied, not
+// converted.  Built per call: the tensors are parameters that change between
+// steps, and the copy is 2C + 1 rows.
+template <typename T>
+struct OperandImages {
+  static int64_t gamma(int C) { (void)C; return 0; }
+  static int64_t beta(int C) { return (int64_t)C * G3H * (int64_t)sizeof(T); }
+  static int64_t bhh(int C) { return 2 * beta(C); }
+  static int64_t total(int C) { return bhh(C) + G3H * 4; }
+};
+
+template <typename T>
+__global__ void gru_operand_images_kernel(const T* __restrict__ gamma,
+                                          const T* __restrict__ beta,
+                                          const float* __restrict__ b_hh,
+                                          T* __restrict__ gamma_pi,
+                                          T* __restrict__ beta_pi,
+                                          float* __restrict__ bhh_pi, int C) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (2 * C + 1) * 48) return;
+  const int r = idx / 48;
+  const int rem = idx % 48;
+  const int src = (rem / 16) * H + rem % 16;        // natural column of element 0
+  const int dst = (rem / 16) * H + (rem % 16) * 8;  // its pi position
+  if (r < 2 * C) {
+    const T* in = (r < C ? gamma + r * G3H : beta + (r - C) * G3H) + src;
+    T* out = (r < C ? gamma_pi + r * G3H : beta_pi + (r - C) * G3H) + dst;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[e] = in[e * 16];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bhh_pi[dst + e] = b_hh[src + e * 16];
   }
 }
 
@@ -1393,6 +1594,22 @@ static hipError_t allow_lds(K kernel, int bytes) {
                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
+// Fills the operand-image buffer (see OperandImages) on the stream.
+template <typename T>
+static hipError_t operand_images_launch(const void* gamma, const void* beta,
+                                        const float* b_hh, void* images, int C,
+                                        hipStream_t stream) {
+  if (images == nullptr) return hipErrorInvalidValue;
+  using I = OperandImages<T>;
+  char* img = static_cast<char*>(images);
+  const int n = (2 * C + 1) * 48;
+  hipLaunchKernelGGL((gru_operand_images_kernel<T>), dim3((n + 255) / 256), dim3(256),
+                     0, stream, (const T*)gamma, (const T*)beta, b_hh,
+                     (T*)(img + I::gamma(C)), (T*)(img + I::beta(C)),
+                     (float*)(img + I::bhh(C)), C);
+  return hipGetLastError();
+}
+
 struct FwdArgs {
   const void *xg, *gamma, *beta, *w_gemm;
   const float* b_hh;
@@ -1403,6 +1620,7 @@ struct FwdArgs {
   void *out, *h_last;      // h_last: decode entry only
   int O;
   const int* lens;         // VARLEN only
+  void* images;            // operand-image buffer (streaming variants fill it)
   hipStream_t stream;
 };
 
@@ -1414,10 +1632,23 @@ static hipError_t gru_fwd_launch(const FwdArgs& a) {
   if (attr != hipSuccess) return attr;
   const int64_t R = (int64_t)a.B * a.C;
   const int grid = (int)((R + ROWS * NSUB - 1) / (ROWS * NSUB));
+  const void *gamma = a.gamma, *beta = a.beta;
+  const float* b_hh = a.b_hh;
+  if constexpr (!fwd_gb_regs<FP8, NSUB, VARLEN>) {
+    // the streaming variants read the pi-ordered images instead
+    if (hipError_t e = operand_images_launch<T>(a.gamma, a.beta, a.b_hh, a.images,
+                                                a.C, a.stream))
+      return e;
+    using I = OperandImages<T>;
+    const char* img = static_cast<const char*>(a.images);
+    gamma = img + I::gamma(a.C);
+    beta = img + I::beta(a.C);
+    b_hh = reinterpret_cast<const float*>(img + I::bhh(a.C));
+  }
   hipLaunchKernelGGL((gru_fwd_kernel<T, SAVE, FP8, NSUB, HEADS, VARLEN>),
                      dim3(grid), dim3(THREADS * NSUB), LDS, a.stream,
-                     (const T*)a.xg, (const T*)a.gamma, (const T*)a.beta,
-                     (const uint16_t*)a.w_gemm, a.b_hh, (const T*)a.h0,
+                     (const T*)a.xg, (const T*)gamma, (const T*)beta,
+                     (const uint16_t*)a.w_gemm, b_hh, (const T*)a.h0,
                      (T*)a.h_all, (T*)a.saves, a.B, a.TT, a.C, a.reverse,
                      (const uint16_t*)a.wh_fwd, (T*)a.out, (T*)a.h_last, a.O,
                      a.lens);
@@ -1431,6 +1662,7 @@ struct BwdArgs {
   void* dpre;
   float* dh0;
   int B, TT, C, reverse, O;
+  void* images;            // operand-image buffer, filled here
   hipStream_t stream;
 };
 
@@ -1442,11 +1674,19 @@ static hipError_t gru_bwd_launch(const BwdArgs& a) {
   if (attr != hipSuccess) return attr;
   const int64_t R = (int64_t)a.B * a.C;
   const int grid = (int)((R + ROWS * NSUB - 1) / (ROWS * NSUB));
+  // gamma / beta reach the kernel as pi-ordered images; b_hh stays natural
+  // (its n slice sits in registers over the whole loop)
+  if (hipError_t e = operand_images_launch<T>(a.gamma, a.beta, a.b_hh, a.images,
+                                              a.C, a.stream))
+    return e;
+  using I = OperandImages<T>;
+  const char* img = static_cast<const char*>(a.images);
   hipLaunchKernelGGL((gru_bwd_kernel<T, NSUB, FUSED>), dim3(grid),
                      dim3(THREADS * NSUB), LDS, a.stream, (const T*)a.grad,
                      (const uint16_t*)a.wh_img, (const uint16_t*)a.w_img,
                      (const uint16_t*)a.w_fwd, (const T*)a.xg,
-                     (const T*)a.gamma, (const T*)a.beta, a.b_hh,
+                     (const T*)(img + I::gamma(a.C)), (const T*)(img + I::beta(a.C)),
+                     a.b_hh,
                      (const T*)a.h0, (const T*)a.h_all, (const T*)a.saves,
                      (T*)a.dpre, a.dh0, a.B, a.TT, a.C, a.reverse, a.O);
   return hipGetLastError();
@@ -1528,6 +1768,15 @@ static hipError_t gru_reduce_launch(const void* dpre, const void* gamma,
 
 extern "C" {
 
+// Bytes of the operand-image buffer that dr_gru_fwd, dr_gru_decode and
+// dr_gru_bwd take as `images`: device memory, 16-byte aligned, contents
+// undefined on entry.  The entries fill and read it on the stream where the
+// variant they pick streams its FiLM operands.
+int64_t dr_gru_operand_images_bytes(int C, int is_bf16) {
+  return is_bf16 ? dr::OperandImages<uint16_t>::total(C)
+                 : dr::OperandImages<float>::total(C);
+}
+
 // 1 when a saving forward at (B, C) runs the quantile-head projection inside
 // the kernel (dr_gru_fwd then takes wh_fwd / out / O), 0 when the caller does
 // the projection itself.
@@ -1547,10 +1796,11 @@ int dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
                const void* w_hh, const float* b_hh, const void* h0, void* h_all,
                void* saves, const void* wh_fwd, void* out, int O, int B, int TT,
                int C, int reverse, int save, int fp8, int is_bf16,
-               hipStream_t stream) {
+               void* images, hipStream_t stream) {
   const bool heads = wh_fwd != nullptr;
   const dr::FwdArgs a{xg, gamma, beta, w_hh, b_hh, h0, h_all, saves, B, TT, C,
-                      reverse, wh_fwd, out, nullptr, heads ? O : 0, nullptr, stream};
+                      reverse, wh_fwd, out, nullptr, heads ? O : 0, nullptr, images,
+                      stream};
   if (heads && !save) return (int)hipErrorInvalidValue;
   return (int)dr::with_io_type(is_bf16, [&](auto io) {
     using T = typename decltype(io)::type;
@@ -1577,9 +1827,9 @@ int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
                   const void* w_hh, const float* b_hh, const void* h0,
                   const void* wh_fwd, void* out, void* h_last, int B, int TT,
                   int C, int O, int reverse, int fp8, int is_bf16,
-                  const int* lens, hipStream_t stream) {
+                  const int* lens, void* images, hipStream_t stream) {
   const dr::FwdArgs a{xg, gamma, beta, w_hh, b_hh, h0, nullptr, nullptr, B, TT, C,
-                      reverse, wh_fwd, out, h_last, O, lens, stream};
+                      reverse, wh_fwd, out, h_last, O, lens, images, stream};
   auto run = [&](auto varlen) {
     return dr::with_io_type(is_bf16, [&](auto io) {
       using T = typename decltype(io)::type;
@@ -1600,12 +1850,12 @@ int dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
                const void* w_fwd, const void* xg, const void* gamma,
                const void* beta, const float* b_hh, const void* h0,
                const void* h_all, const void* saves, void* dpre, float* dh0,
-               int B, int TT, int C, int reverse, int is_bf16,
+               int B, int TT, int C, int reverse, int is_bf16, void* images,
                hipStream_t stream) {
   const bool fused = wh_img != nullptr;
   const dr::BwdArgs a{grad, wh_img, w_img, w_fwd, xg, gamma, beta, b_hh, h0,
                       h_all, saves, dpre, dh0, B, TT, C, reverse, fused ? O : 0,
-                      stream};
+                      images, stream};
   // enough 128-row tiles to fill the chip at 1 block/CU: the LDS-W variant
   const int64_t tiles128 = ((int64_t)B * C + 2 * dr::ROWS - 1) / (2 * dr::ROWS);
   const bool lds_w = tiles128 >= 192;
