@@ -1,7 +1,14 @@
-// Fused multi-head attention forward for gfx950 (flash-style, MFMA).
+// Fused multi-head attention for gfx950 (MFMA), forward and backward.
 //
-// One workgroup (4 waves) per 64-row Q tile of one (batch, head): QK^T on
-// v_mfma_f32_16x16x32_bf16 with the K tile staged in LDS (rows padded +16 B
+// Two sets of bodies behind one launcher (mha_whole_tile, near the end): the
+// whole-head tile kernels for T <= 64, and the flash-style kernels below for
+// everything else.  All of them address q, k, v, o by (batch, head, time)
+// element strides, so they run on (B, H, T, D) tensors and on the packed qkv
+// projection (B, T, 3, H, D) alike.
+//
+// Flash-style forward: one workgroup (4 waves) per 64-row Q tile of one
+// (batch, head): QK^T on v_mfma_f32_16x16x32_bf16 with the K tile staged in
+// LDS (rows padded +16 B
 // so the 16-lane ds_read_b128 groups land on distinct banks), online softmax
 // entirely in registers (running row max/denominator, rescale-on-grow), PV
 // on MFMA with V staged transposed.  No S x S score tensor ever exists in
@@ -26,6 +33,13 @@ constexpr int K_STRIDE = DMAX * 2 + 16;      // K tile: [key][d]
 constexpr int V_STRIDE = KT_KEYS * 2 + 16;   // V^T tile: [d][key]
 constexpr int P_STRIDE = KT_KEYS * 2 + 16;   // P tile:  [qrow][key]
 
+// Element strides of a (batch, head, time, d) operand with unit d stride.
+// (B, H, T, D) contiguous: {H*T*D, T*D, D}; the q / k / v parts of a packed
+// (B, T, 3, H, D) qkv: {T*3*H*D, D, 3*H*D}; a (B, T, H*D) output: {T*H*D, D, H*D}.
+struct MhaStrides {
+  int64_t sb, sh, st;
+};
+
 // VARLEN = true (inference only): sample b = bh / n_heads is valid at
 // t < L = clamp(kv_len[b], 1, T_len).  Keys >= L are absent (never staged,
 // never scored), query tiles at or past L store zeros and leave before the
@@ -33,11 +47,12 @@ constexpr int P_STRIDE = KT_KEYS * 2 + 16;   // P tile:  [qrow][key]
 // using T_len.
 template <typename T, bool VARLEN = false>
 __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
-    const T* __restrict__ q,   // (BH, T, D)
+    const T* __restrict__ q,   // element (b, h, t, d) at b*sb + h*sh + t*st + d
     const T* __restrict__ k,
     const T* __restrict__ v,
-    T* __restrict__ o,         // (BH, T, D)
+    T* __restrict__ o,         // same, with the strides `os`
     float* __restrict__ lse,   // (BH, T)
+    MhaStrides qs, MhaStrides os,
     int T_len, int D, float scale,
     const int* __restrict__ kv_len,  // VARLEN: (B,) int32
     int n_heads) {
@@ -51,9 +66,11 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
   const int64_t bh = blockIdx.y;
   const int q0 = blockIdx.x * QT;
 
-  const T* qb = q + bh * T_len * D;
-  const T* kb = k + bh * T_len * D;
-  const T* vb = v + bh * T_len * D;
+  const int64_t in_off = (bh / n_heads) * qs.sb + (bh % n_heads) * qs.sh;
+  const T* qb = q + in_off;
+  const T* kb = k + in_off;
+  const T* vb = v + in_off;
+  T* ob = o + (bh / n_heads) * os.sb + (bh % n_heads) * os.sh;
 
   const int c_col = lane & 15;
   const int rgrp = lane >> 4;
@@ -70,7 +87,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
           int d = nt * 16 + c_col;
-          if (d < D) stf(o + (bh * T_len + row) * D + d, 0.f);
+          if (d < D) stf(ob + (int64_t)row * os.st + d, 0.f);
         }
         if (c_col == 0) lse[bh * T_len + row] = 0.f;
       }
@@ -89,7 +106,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         int d = kt * 32 + rgrp * 8 + j;
-        float val = (qrow < L && d < D) ? ldf(qb + (int64_t)qrow * D + d) : 0.f;
+        float val = (qrow < L && d < D) ? ldf(qb + (int64_t)qrow * qs.st + d) : 0.f;
         tmp[j] = f2bf(val);
       }
       qfrag[kt] = *reinterpret_cast<bf16x8*>(tmp);
@@ -123,7 +140,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         int d = blk * 8 + e;
-        dst[e] = f2bf((krow < L && d < D) ? ldf(kb + (int64_t)krow * D + d) : 0.f);
+        dst[e] = f2bf((krow < L && d < D) ? ldf(kb + (int64_t)krow * qs.st + d) : 0.f);
       }
     }
     for (int id = tid; id < DMAX * KT_KEYS / 8; id += A_THREADS) {
@@ -133,7 +150,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         int key = key0 + kb8 * 8 + e;
-        dst[e] = f2bf((key < L && d < D) ? ldf(vb + (int64_t)key * D + d) : 0.f);
+        dst[e] = f2bf((key < L && d < D) ? ldf(vb + (int64_t)key * qs.st + d) : 0.f);
       }
     }
     __syncthreads();
@@ -233,7 +250,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
       if (nt >= n_d_tiles) continue;
       int d = nt * 16 + c_col;
       if (d < D)
-        stf(o + (bh * T_len + row) * D + d, pad ? 0.f : o_acc[nt][i] * inv_l);
+        stf(ob + (int64_t)row * os.st + d, pad ? 0.f : o_acc[nt][i] * inv_l);
     }
     if (c_col == 0)
       lse[bh * T_len + row] =
@@ -250,16 +267,17 @@ __global__ __launch_bounds__(A_THREADS) void mha_fwd_kernel(
 // dQ contributions scatter with fp32 atomics (few per block at these T).
 template <typename T>
 __global__ __launch_bounds__(A_THREADS) void mha_bwd_kernel(
-    const T* __restrict__ q,    // (BH, T, D)
+    const T* __restrict__ q,    // strides qs (as in mha_fwd_kernel)
     const T* __restrict__ k,
     const T* __restrict__ v,
-    const T* __restrict__ o,
-    const T* __restrict__ dout,
+    const T* __restrict__ o,    // strides os
+    const T* __restrict__ dout, // strides os
     const float* __restrict__ lse,   // (BH, T)
-    float* __restrict__ dq,          // (BH, T, D) fp32 (atomic accumulate)
-    T* __restrict__ dk,              // (BH, T, D)
+    float* __restrict__ dq,          // strides dqs, fp32 (atomic accumulate)
+    T* __restrict__ dk,              // strides qs
     T* __restrict__ dv,
-    int T_len, int D, float scale) {
+    MhaStrides qs, MhaStrides os, MhaStrides dqs,
+    int T_len, int D, float scale, int n_heads) {
   // LDS: q / do tiles (32 x D bf16, padded rows) + per-wave P/ds scratch +
   // per-q-tile lse/Drow
   __shared__ __attribute__((aligned(16))) char q_lds[32 * K_STRIDE];
@@ -274,11 +292,17 @@ __global__ __launch_bounds__(A_THREADS) void mha_bwd_kernel(
   const int64_t bh = blockIdx.y;
   const int key0 = blockIdx.x * 64 + wv * 16;  // this wave's 16 keys
 
-  const T* qb = q + bh * T_len * D;
-  const T* kb = k + bh * T_len * D;
-  const T* vb = v + bh * T_len * D;
-  const T* ob = o + bh * T_len * D;
-  const T* dob = dout + bh * T_len * D;
+  const int64_t bb = bh / n_heads, hh = bh % n_heads;
+  const int64_t in_off = bb * qs.sb + hh * qs.sh;
+  const int64_t o_off = bb * os.sb + hh * os.sh;
+  const T* qb = q + in_off;
+  const T* kb = k + in_off;
+  const T* vb = v + in_off;
+  const T* ob = o + o_off;
+  const T* dob = dout + o_off;
+  float* dqb = dq + bb * dqs.sb + hh * dqs.sh;
+  T* dkb = dk + in_off;
+  T* dvb = dv + in_off;
 
   const int c_col = lane & 15;
   const int rgrp = lane >> 4;
@@ -295,8 +319,8 @@ __global__ __launch_bounds__(A_THREADS) void mha_bwd_kernel(
     for (int j = 0; j < 8; ++j) {
       int d = kt * 32 + rgrp * 8 + j;
       bool ok = krow < T_len && d < D;
-      tk[j] = f2bf(ok ? ldf(kb + (int64_t)krow * D + d) : 0.f);
-      tv[j] = f2bf(ok ? ldf(vb + (int64_t)krow * D + d) : 0.f);
+      tk[j] = f2bf(ok ? ldf(kb + (int64_t)krow * qs.st + d) : 0.f);
+      tv[j] = f2bf(ok ? ldf(vb + (int64_t)krow * qs.st + d) : 0.f);
     }
     kfrag[kt] = *reinterpret_cast<bf16x8*>(tk);
     vfrag[kt] = *reinterpret_cast<bf16x8*>(tv);
@@ -327,8 +351,8 @@ __global__ __launch_bounds__(A_THREADS) void mha_bwd_kernel(
       for (int e = 0; e < 8; ++e) {
         int d = blk * 8 + e;
         bool ok = qrow < T_len && d < D;
-        dstq[e] = f2bf(ok ? ldf(qb + (int64_t)qrow * D + d) : 0.f);
-        dstd[e] = f2bf(ok ? ldf(dob + (int64_t)qrow * D + d) : 0.f);
+        dstq[e] = f2bf(ok ? ldf(qb + (int64_t)qrow * qs.st + d) : 0.f);
+        dstd[e] = f2bf(ok ? ldf(dob + (int64_t)qrow * os.st + d) : 0.f);
       }
     }
     // Drow[r] = sum_d do[r,d] * o[r,d]; lse per row (one wave's worth of rows)
@@ -337,7 +361,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_bwd_kernel(
       float s = 0.f;
       if (qrow < T_len) {
         for (int d = 0; d < D; ++d)
-          s += ldf(dob + (int64_t)qrow * D + d) * ldf(ob + (int64_t)qrow * D + d);
+          s += ldf(dob + (int64_t)qrow * os.st + d) * ldf(ob + (int64_t)qrow * os.st + d);
         lse_s[tid] = lse[bh * T_len + qrow];
       } else {
         lse_s[tid] = 0.f;
@@ -485,7 +509,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_bwd_kernel(
           int keyr = rgrp * 8 + j;
           int krow = key0 + keyr;
           bool ok = keyr < 16 && krow < T_len && d < D;
-          bk[j] = f2bf(ok ? ldf(kb + (int64_t)krow * D + d) : 0.f);
+          bk[j] = f2bf(ok ? ldf(kb + (int64_t)krow * qs.st + d) : 0.f);
         }
         bf16x8 bfrag = *reinterpret_cast<bf16x8*>(bk);
         f32x4 a = {0.f, 0.f, 0.f, 0.f};
@@ -496,7 +520,7 @@ __global__ __launch_bounds__(A_THREADS) void mha_bwd_kernel(
           int qrow = q0 + qh * 16 + rgrp * 4 + i;
           int d2 = nt * 16 + c_col;
           if (qrow < T_len && d2 < D)
-            atomicAdd(dq + (bh * T_len + qrow) * D + d2, a[i]);
+            atomicAdd(dqb + (int64_t)qrow * dqs.st + d2, a[i]);
         }
       }
     }
@@ -512,66 +536,528 @@ __global__ __launch_bounds__(A_THREADS) void mha_bwd_kernel(
       if (nt >= n_d_tiles) continue;
       int d = nt * 16 + c_col;
       if (d < D) {
-        stf(dk + (bh * T_len + krow) * D + d, dk_acc[nt][i]);
-        stf(dv + (bh * T_len + krow) * D + d, dv_acc[nt][i]);
+        stf(dkb + (int64_t)krow * qs.st + d, dk_acc[nt][i]);
+        stf(dvb + (int64_t)krow * qs.st + d, dv_acc[nt][i]);
       }
     }
   }
 }
 
+// ------------------------------------------------- whole head in one tile
+// T <= 64: one WAVE holds all queries and all keys of one (batch, head), padded
+// to 64 rows.  Every global access is one 16-byte piece of a (t, head) row per
+// lane (f32 IO: two loads / one 16-byte store); an MFMA fragment of q, k, v or
+// dO (row = lane & 15, 8 consecutive d) is that load itself.  A wave reads only
+// LDS it wrote, so there is no block barrier: wave_lds_fence() orders the
+// image stores ahead of the transposed reads.  The 4 waves of a block are 4
+// independent heads.
+//
+// A score accumulator tile is the next product's B operand without leaving its
+// lane: lane (c = lane & 15, g = lane >> 4) holds rows 4g .. 4g+3 of column c,
+// so the two row tiles of a 32-row k-step give element j of the fragment the
+// row perm(g, j) = 16 (j >> 2) + 4g + (j & 3).  The A operand follows that
+// order: it is read with ds_read_b64_tr_b16 from a row-major [row][d] image,
+// blocks of rows 16 jj + 4g .. + 3 (jj = j >> 2).  All 64 lanes issue every
+// transposed read, with an in-bounds address of the padded image.
+constexpr int TILE_T = 64;
+constexpr int DS_STRIDE = 2 * TILE_T + 8;   // dS^T image row: [key][64 q] + 8 B
+
+using s16x4 = __attribute__((ext_vector_type(4))) short;
+
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// 8 consecutive elements as floats; ok == false: zeros, nothing is read
+__device__ __forceinline__ void ld8f(const uint16_t* p, bool ok, float v[8]) {
+  uint4 u = make_uint4(0u, 0u, 0u, 0u);
+  if (ok) u = *reinterpret_cast<const uint4*>(p);
+  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = bf2f((uint16_t)(w[i] & 0xffff));
+    v[2 * i + 1] = bf2f((uint16_t)(w[i] >> 16));
+  }
+}
+__device__ __forceinline__ void ld8f(const float* p, bool ok, float v[8]) {
+  float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+  if (ok) {
+    a = *reinterpret_cast<const float4*>(p);
+    b = *reinterpret_cast<const float4*>(p + 4);
+  }
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+__device__ __forceinline__ bf16x8 pack8(const float v[8]) {
+  uint4 u = make_uint4(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]),
+                       f2bf2(v[6], v[7]));
+  return *reinterpret_cast<bf16x8*>(&u);
+}
+
+// 8 consecutive elements as an MFMA fragment; bf16 IO: the 16 bytes as loaded
+__device__ __forceinline__ bf16x8 ld8(const uint16_t* p, bool ok) {
+  uint4 u = make_uint4(0u, 0u, 0u, 0u);
+  if (ok) u = *reinterpret_cast<const uint4*>(p);
+  return *reinterpret_cast<bf16x8*>(&u);
+}
+__device__ __forceinline__ bf16x8 ld8(const float* p, bool ok) {
+  float v[8];
+  ld8f(p, ok, v);
+  return pack8(v);
+}
+
+// two accumulator tiles (rows 0..15 and 16..31 of a 32-row k-step) as the B
+// fragment of that k-step, in the perm(g, j) order
+__device__ __forceinline__ bf16x8 acc_pair_frag(const float lo[4], const float hi[4]) {
+  uint4 u = make_uint4(f2bf2(lo[0], lo[1]), f2bf2(lo[2], lo[3]), f2bf2(hi[0], hi[1]),
+                       f2bf2(hi[2], hi[3]));
+  return *reinterpret_cast<bf16x8*>(&u);
+}
+
+// One transposed read: `p` is this lane's address of 4 consecutive elements of
+// its block row (row lane_c >> 2, columns 4 (lane_c & 3) ..); the lane gets
+// column lane_c of the block's 4 rows.
+__device__ __forceinline__ s16x4 lds_tr(const char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) s16x4*)(p));
+}
+
+// A (or B) fragment of one k-step from a row-major image with `stride` bytes per
+// row: rows r0 + hi_step * jj + 4 * (this lane's share) of columns col0 .. + 15
+__device__ __forceinline__ bf16x8 lds_tr_frag(const char* img, int stride, int row_lo,
+                                              int row_hi, int col0, int lane) {
+  const int c = lane & 15;
+  const int in_blk = (c >> 2) * stride + (col0 + 4 * (c & 3)) * 2;
+  s16x4 a = lds_tr(img + row_lo * stride + in_blk);
+  s16x4 b = lds_tr(img + row_hi * stride + in_blk);
+  s16x8 r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  return *reinterpret_cast<bf16x8*>(&r);
+}
+
+template <typename T, int DH>
+__global__ __launch_bounds__(A_THREADS) void mha_tile_fwd_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
+    T* __restrict__ o, float* __restrict__ lse, MhaStrides qs, MhaStrides os,
+    int64_t BH, int n_heads, int T_len, float scale) {
+  constexpr int KS = (DH + 31) / 32;   // k-steps over d in the score product
+  constexpr int DT = DH / 16;          // 16-wide d tiles of the output
+  constexpr int CH = DH / 8;           // 16-byte pieces per row
+  constexpr int ROWB = DH * 2;         // image row, bytes
+  __shared__ __attribute__((aligned(16))) char lds[A_WAVES][TILE_T * ROWB];
+
+  const int wv = threadIdx.x / DR_WAVE;
+  const int lane = threadIdx.x % DR_WAVE;
+  const int64_t bh = (int64_t)blockIdx.x * A_WAVES + wv;
+  if (bh >= BH) return;                // wave-uniform
+  char* v_img = lds[wv];
+
+  const int64_t in_off = (bh / n_heads) * qs.sb + (bh % n_heads) * qs.sh;
+  const T* qb = q + in_off;
+  const T* kb = k + in_off;
+  const T* vb = v + in_off;
+  T* ob = o + (bh / n_heads) * os.sb + (bh % n_heads) * os.sh;
+  const int c = lane & 15, g = lane >> 4;
+
+  // ---- q / k fragments straight from global, V into its row-major image ----
+  bf16x8 qf[4][KS], kf[4][KS];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int row = 16 * i + c, d0 = 32 * ks + 8 * g;
+      const bool ok = row < T_len && d0 < DH;
+      qf[i][ks] = ld8(qb + (int64_t)row * qs.st + d0, ok);
+      kf[i][ks] = ld8(kb + (int64_t)row * qs.st + d0, ok);
+    }
+#pragma unroll
+  for (int it = 0; it < CH; ++it) {
+    const int id = it * DR_WAVE + lane;
+    const int row = id / CH, ch = id % CH;
+    *reinterpret_cast<bf16x8*>(v_img + row * ROWB + ch * 16) =
+        ld8(vb + (int64_t)row * qs.st + ch * 8, row < T_len);
+  }
+  wave_lds_fence();
+
+  // ---- S^T[key][q]: rows = keys (16 ki + 4g + r), lane column = q ----
+  float p[4][4][4];                    // [qi][ki][r]
+#pragma unroll
+  for (int qi = 0; qi < 4; ++qi)
+#pragma unroll
+    for (int ki = 0; ki < 4; ++ki) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ki][ks], qf[qi][ks], a, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        p[qi][ki][r] = (16 * ki + 4 * g + r < T_len) ? a[r] * scale : -1e30f;
+    }
+
+  // ---- softmax of each query column: once, over all keys ----
+  float m[4], l[4];
+  bf16x8 pf[2][4];                     // [k-step over keys][qi]
+#pragma unroll
+  for (int qi = 0; qi < 4; ++qi) {
+    float mx = -1e30f;
+#pragma unroll
+    for (int ki = 0; ki < 4; ++ki)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, p[qi][ki][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 16, DR_WAVE));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, DR_WAVE));
+    float sum = 0.f;
+#pragma unroll
+    for (int ki = 0; ki < 4; ++ki)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        p[qi][ki][r] = __expf(p[qi][ki][r] - mx);
+        sum += p[qi][ki][r];
+      }
+    sum += __shfl_xor(sum, 16, DR_WAVE);
+    sum += __shfl_xor(sum, 32, DR_WAVE);
+    m[qi] = mx;
+    l[qi] = sum;
+    pf[0][qi] = acc_pair_frag(p[qi][0], p[qi][1]);
+    pf[1][qi] = acc_pair_frag(p[qi][2], p[qi][3]);
+  }
+
+  // ---- O^T[d][q] = V^T P^T: rows = d (16 dt + 4g + r), lane column = q ----
+  f32x4 o_acc[DT][4];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+#pragma unroll
+    for (int qi = 0; qi < 4; ++qi) o_acc[dt][qi] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const bf16x8 vt = lds_tr_frag(v_img, ROWB, 32 * s + 4 * g, 32 * s + 16 + 4 * g,
+                                    16 * dt, lane);
+#pragma unroll
+      for (int qi = 0; qi < 4; ++qi)
+        o_acc[dt][qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pf[s][qi],
+                                                                o_acc[dt][qi], 0, 0, 0);
+    }
+  }
+
+  // ---- store: 4 consecutive d of one (t, head) row per lane ----
+#pragma unroll
+  for (int qi = 0; qi < 4; ++qi) {
+    const int row = 16 * qi + c;
+    if (row >= T_len) continue;
+    const float inv_l = 1.f / l[qi];   // l >= 1: the row maximum contributes 1
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      const float out[4] = {o_acc[dt][qi][0] * inv_l, o_acc[dt][qi][1] * inv_l,
+                            o_acc[dt][qi][2] * inv_l, o_acc[dt][qi][3] * inv_l};
+      st4(ob + (int64_t)row * os.st + 16 * dt + 4 * g, out);
+    }
+    if (g == 0) lse[bh * T_len + row] = m[qi] + __logf(l[qi]);
+  }
+}
+
+// Backward of the whole-head tile.  Scores are queries-on-rows here
+// (S[q][key], lane column = key), so P and dS feed dV^T = dO^T P and
+// dK^T = Q^T dS from their accumulators; dQ^T = K^T dS^T sums over the lane
+// index and takes dS through one LDS image ([key][q], 8-byte stores, transposed
+// reads).  Nothing is accumulated across waves: no atomics, dq in the IO dtype.
+// LDS per wave: phase 1 the Q and dO images, phase 2 (over them) the K and
+// dS^T images; all four are written from the fragments already in registers.
+template <int DH>
+struct TileBwdLds {
+  static constexpr int IMG = TILE_T * DH * 2;
+  static constexpr int DS = TILE_T * DS_STRIDE;
+  static constexpr int BYTES = IMG + (IMG > DS ? IMG : DS);
+};
+
+template <typename T, int DH>
+__global__ __launch_bounds__(A_THREADS) void mha_tile_bwd_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
+    const T* __restrict__ o, const T* __restrict__ dout,
+    const float* __restrict__ lse, T* __restrict__ dq, T* __restrict__ dk,
+    T* __restrict__ dv, MhaStrides qs, MhaStrides os, int64_t BH, int n_heads,
+    int T_len, float scale) {
+  constexpr int KS = (DH + 31) / 32;
+  constexpr int DT = DH / 16;
+  constexpr int ROWB = DH * 2;
+  constexpr int IMG = TileBwdLds<DH>::IMG;
+  __shared__ __attribute__((aligned(16))) char lds[A_WAVES][TileBwdLds<DH>::BYTES];
+  __shared__ __attribute__((aligned(16))) float stat[A_WAVES][2 * TILE_T];
+
+  const int wv = threadIdx.x / DR_WAVE;
+  const int lane = threadIdx.x % DR_WAVE;
+  const int64_t bh = (int64_t)blockIdx.x * A_WAVES + wv;
+  if (bh >= BH) return;                // wave-uniform
+  char* img0 = lds[wv];                // Q image, then K image
+  char* img1 = lds[wv] + IMG;          // dO image, then dS^T image
+  float* lse_s = stat[wv];
+  float* drow_s = stat[wv] + TILE_T;
+
+  const int64_t bb = bh / n_heads, hh = bh % n_heads;
+  const int64_t in_off = bb * qs.sb + hh * qs.sh;
+  const int64_t o_off = bb * os.sb + hh * os.sh;
+  const T* qb = q + in_off;
+  const T* kb = k + in_off;
+  const T* vb = v + in_off;
+  const T* ob = o + o_off;
+  const T* dob = dout + o_off;
+  const int c = lane & 15, g = lane >> 4;
+
+  // ---- fragments from global; Drow = rowsum(dO * O) from the same loads ----
+  bf16x8 qf[4][KS], kf[4][KS], vf[4][KS], dof[4][KS];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float dsum = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int row = 16 * i + c, d0 = 32 * ks + 8 * g;
+      const bool ok = row < T_len && d0 < DH;
+      qf[i][ks] = ld8(qb + (int64_t)row * qs.st + d0, ok);
+      kf[i][ks] = ld8(kb + (int64_t)row * qs.st + d0, ok);
+      vf[i][ks] = ld8(vb + (int64_t)row * qs.st + d0, ok);
+      float a[8], b[8];
+      ld8f(dob + (int64_t)row * os.st + d0, ok, a);
+      ld8f(ob + (int64_t)row * os.st + d0, ok, b);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dsum += a[e] * b[e];
+      dof[i][ks] = pack8(a);
+      if (d0 < DH) {
+        *reinterpret_cast<bf16x8*>(img0 + row * ROWB + d0 * 2) = qf[i][ks];
+        *reinterpret_cast<bf16x8*>(img1 + row * ROWB + d0 * 2) = dof[i][ks];
+      }
+    }
+    // the 4 lanes of a row hold its DH / 8 pieces
+    dsum += __shfl_xor(dsum, 16, DR_WAVE);
+    dsum += __shfl_xor(dsum, 32, DR_WAVE);
+    if (g == 0) drow_s[16 * i + c] = dsum;
+  }
+  lse_s[lane] = lane < T_len ? lse[bh * T_len + lane] : 0.f;
+  wave_lds_fence();
+
+  // ---- P and dS, [q][key]: rows = q (16 qi + 4g + r), lane column = key ----
+  bf16x8 pf[2][4], dsf[2][4];          // [k-step over q][ki]
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int ki = 0; ki < 4; ++ki) {
+      float pp[2][4], dd[2][4];
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int qi = 2 * s + half;
+        f32x4 sa = {0.f, 0.f, 0.f, 0.f}, da = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[qi][ks], kf[ki][ks], sa, 0, 0, 0);
+          da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof[qi][ks], vf[ki][ks], da, 0, 0, 0);
+        }
+        const float4 l4 = *reinterpret_cast<const float4*>(lse_s + 16 * qi + 4 * g);
+        const float4 r4 = *reinterpret_cast<const float4*>(drow_s + 16 * qi + 4 * g);
+        const float lv[4] = {l4.x, l4.y, l4.z, l4.w};
+        const float rv[4] = {r4.x, r4.y, r4.z, r4.w};
+        const bool kok = 16 * ki + c < T_len;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool ok = kok && (16 * qi + 4 * g + r < T_len);
+          const float pv = ok ? __expf(sa[r] * scale - lv[r]) : 0.f;
+          pp[half][r] = pv;
+          dd[half][r] = ok ? pv * (da[r] - rv[r]) * scale : 0.f;
+        }
+      }
+      pf[s][ki] = acc_pair_frag(pp[0], pp[1]);
+      dsf[s][ki] = acc_pair_frag(dd[0], dd[1]);
+    }
+
+  // ---- dV^T = dO^T P, dK^T = Q^T dS: rows = d, lane column = key ----
+  T* dkb = dk + in_off;
+  T* dvb = dv + in_off;
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    f32x4 dv_acc[4], dk_acc[4];
+#pragma unroll
+    for (int ki = 0; ki < 4; ++ki) {
+      dv_acc[ki] = f32x4{0.f, 0.f, 0.f, 0.f};
+      dk_acc[ki] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const bf16x8 dot = lds_tr_frag(img1, ROWB, 32 * s + 4 * g, 32 * s + 16 + 4 * g,
+                                     16 * dt, lane);
+      const bf16x8 qt = lds_tr_frag(img0, ROWB, 32 * s + 4 * g, 32 * s + 16 + 4 * g,
+                                    16 * dt, lane);
+#pragma unroll
+      for (int ki = 0; ki < 4; ++ki) {
+        dv_acc[ki] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot, pf[s][ki], dv_acc[ki], 0, 0, 0);
+        dk_acc[ki] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt, dsf[s][ki], dk_acc[ki], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int ki = 0; ki < 4; ++ki) {
+      const int row = 16 * ki + c;
+      if (row >= T_len) continue;
+      const float a[4] = {dv_acc[ki][0], dv_acc[ki][1], dv_acc[ki][2], dv_acc[ki][3]};
+      const float b[4] = {dk_acc[ki][0], dk_acc[ki][1], dk_acc[ki][2], dk_acc[ki][3]};
+      st4(dvb + (int64_t)row * qs.st + 16 * dt + 4 * g, a);
+      st4(dkb + (int64_t)row * qs.st + 16 * dt + 4 * g, b);
+    }
+  }
+
+  // ---- phase 2 images over phase 1's: K [key][d], dS^T [key][q] ----
+  wave_lds_fence();                    // the Q / dO image reads are done
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int d0 = 32 * ks + 8 * g;
+      if (d0 < DH)
+        *reinterpret_cast<bf16x8*>(img0 + (16 * i + c) * ROWB + d0 * 2) = kf[i][ks];
+    }
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int ki = 0; ki < 4; ++ki) {
+      // rows q = 32 s + 4g .. + 3 and 32 s + 16 + 4g .. + 3 of key column 16 ki + c
+      const uint4 u = *reinterpret_cast<const uint4*>(&dsf[s][ki]);
+      char* dst = img1 + (16 * ki + c) * DS_STRIDE + (32 * s + 4 * g) * 2;
+      *reinterpret_cast<uint2*>(dst) = make_uint2(u.x, u.y);
+      *reinterpret_cast<uint2*>(dst + 32) = make_uint2(u.z, u.w);
+    }
+  wave_lds_fence();
+
+  // ---- dQ^T = K^T dS^T: rows = d, lane column = q; natural key order ----
+  T* dqb = dq + in_off;
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    f32x4 dq_acc[4];
+#pragma unroll
+    for (int qi = 0; qi < 4; ++qi) dq_acc[qi] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const bf16x8 kt = lds_tr_frag(img0, ROWB, 32 * s + 8 * g, 32 * s + 8 * g + 4,
+                                    16 * dt, lane);
+#pragma unroll
+      for (int qi = 0; qi < 4; ++qi) {
+        const bf16x8 dst = lds_tr_frag(img1, DS_STRIDE, 32 * s + 8 * g,
+                                       32 * s + 8 * g + 4, 16 * qi, lane);
+        dq_acc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt, dst, dq_acc[qi], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int qi = 0; qi < 4; ++qi) {
+      const int row = 16 * qi + c;
+      if (row >= T_len) continue;
+      const float a[4] = {dq_acc[qi][0], dq_acc[qi][1], dq_acc[qi][2], dq_acc[qi][3]};
+      st4(dqb + (int64_t)row * qs.st + 16 * dt + 4 * g, a);
+    }
+  }
+}
+
+// The one place that chooses the kernels: the whole-head tile bodies where all
+// keys and queries of a head fit one wave, the flash-style bodies otherwise
+// (and always with per-sample lengths).
+static bool mha_whole_tile(int T_len, int D) {
+  return T_len >= 1 && T_len <= TILE_T && (D == 16 || D == 32 || D == 64);
+}
+
 template <typename T>
 static void mha_fwd_launch_t(const void* q, const void* k, const void* v, void* o,
-                             float* lse, int64_t BH, int T_len, int D, float scale,
-                             const int* kv_len, int n_heads, hipStream_t stream) {
+                             float* lse, int64_t B, int n_heads, int T_len, int D,
+                             float scale, const int* kv_len, MhaStrides qs,
+                             MhaStrides os, hipStream_t stream) {
+  const int64_t BH = B * n_heads;
+  if (kv_len == nullptr && mha_whole_tile(T_len, D)) {
+    dim3 grid((unsigned)((BH + A_WAVES - 1) / A_WAVES));
+#define DR_MHA_TILE_FWD(DH_)                                                     \
+  hipLaunchKernelGGL((mha_tile_fwd_kernel<T, DH_>), grid, dim3(A_THREADS), 0,    \
+                     stream, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse,  \
+                     qs, os, BH, n_heads, T_len, scale)
+    if (D == 16) DR_MHA_TILE_FWD(16);
+    else if (D == 32) DR_MHA_TILE_FWD(32);
+    else DR_MHA_TILE_FWD(64);
+#undef DR_MHA_TILE_FWD
+    return;
+  }
   dim3 grid((T_len + QT - 1) / QT, (unsigned)BH);
   if (kv_len != nullptr)
     hipLaunchKernelGGL((mha_fwd_kernel<T, true>), grid, dim3(A_THREADS), 0,
                        stream, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse,
-                       T_len, D, scale, kv_len, n_heads);
+                       qs, os, T_len, D, scale, kv_len, n_heads);
   else
     hipLaunchKernelGGL((mha_fwd_kernel<T, false>), grid, dim3(A_THREADS), 0,
                        stream, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse,
-                       T_len, D, scale, nullptr, n_heads);
+                       qs, os, T_len, D, scale, nullptr, n_heads);
 }
 
 template <typename T>
 static void mha_bwd_launch_t(const void* q, const void* k, const void* v,
                              const void* o, const void* dout, const float* lse,
-                             float* dq, void* dk, void* dv, int64_t BH, int T_len,
-                             int D, float scale, hipStream_t stream) {
+                             void* dq, void* dk, void* dv, int64_t B, int n_heads,
+                             int T_len, int D, float scale, MhaStrides qs,
+                             MhaStrides os, MhaStrides dqs, hipStream_t stream) {
+  const int64_t BH = B * n_heads;
+  if (mha_whole_tile(T_len, D)) {
+    dim3 grid((unsigned)((BH + A_WAVES - 1) / A_WAVES));
+#define DR_MHA_TILE_BWD(DH_)                                                     \
+  hipLaunchKernelGGL((mha_tile_bwd_kernel<T, DH_>), grid, dim3(A_THREADS), 0,    \
+                     stream, (const T*)q, (const T*)k, (const T*)v, (const T*)o, \
+                     (const T*)dout, lse, (T*)dq, (T*)dk, (T*)dv, qs, os, BH,    \
+                     n_heads, T_len, scale)
+    if (D == 16) DR_MHA_TILE_BWD(16);
+    else if (D == 32) DR_MHA_TILE_BWD(32);
+    else DR_MHA_TILE_BWD(64);
+#undef DR_MHA_TILE_BWD
+    return;
+  }
   dim3 grid((T_len + 63) / 64, (unsigned)BH);
   hipLaunchKernelGGL((mha_bwd_kernel<T>), grid, dim3(A_THREADS), 0, stream,
                      (const T*)q, (const T*)k, (const T*)v, (const T*)o,
-                     (const T*)dout, lse, dq, (T*)dk, (T*)dv, T_len, D, scale);
+                     (const T*)dout, lse, (float*)dq, (T*)dk, (T*)dv, qs, os, dqs,
+                     T_len, D, scale, n_heads);
 }
+
+static MhaStrides mha_strides(const int64_t* s) { return MhaStrides{s[0], s[1], s[2]}; }
 
 }  // namespace dr
 
 extern "C" {
 
+// 1: dr_mha_bwd at these sizes writes dq itself, in the IO dtype and with the
+// q strides (no atomics); 0: it accumulates into a zeroed fp32 dq with the
+// strides dq_strides.
+int dr_mha_bwd_writes_dq(int T_len, int D) { return dr::mha_whole_tile(T_len, D) ? 1 : 0; }
+
+// *_strides: {batch, head, time} element strides (MhaStrides); q, k, v, dk, dv
+// (and a dq written in the IO dtype) share qkv_strides, o and dout o_strides.
 void dr_mha_bwd(const void* q, const void* k, const void* v, const void* o,
-                const void* dout, const float* lse, float* dq, void* dk, void* dv,
-                int64_t BH, int T_len, int D, float scale, int is_bf16,
-                hipStream_t stream) {
+                const void* dout, const float* lse, void* dq, void* dk, void* dv,
+                int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
+                const int64_t* qkv_strides, const int64_t* o_strides,
+                const int64_t* dq_strides, hipStream_t stream) {
+  const dr::MhaStrides qs = dr::mha_strides(qkv_strides);
+  const dr::MhaStrides os = dr::mha_strides(o_strides);
+  const dr::MhaStrides dqs = dr::mha_strides(dq_strides);
   if (is_bf16)
-    dr::mha_bwd_launch_t<uint16_t>(q, k, v, o, dout, lse, dq, dk, dv, BH, T_len,
-                                   D, scale, stream);
+    dr::mha_bwd_launch_t<uint16_t>(q, k, v, o, dout, lse, dq, dk, dv, B, n_heads,
+                                   T_len, D, scale, qs, os, dqs, stream);
   else
-    dr::mha_bwd_launch_t<float>(q, k, v, o, dout, lse, dq, dk, dv, BH, T_len,
-                                D, scale, stream);
+    dr::mha_bwd_launch_t<float>(q, k, v, o, dout, lse, dq, dk, dv, B, n_heads,
+                                T_len, D, scale, qs, os, dqs, stream);
 }
 
-// kv_len == nullptr: every sample is T_len long (the training kernel).
-// Otherwise (B,) int32 per-sample lengths on the device, BH = B * n_heads.
+// kv_len == nullptr: every sample is T_len long (the training kernels).
+// Otherwise (B,) int32 per-sample lengths on the device.
 void dr_mha_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
-                int64_t BH, int T_len, int D, float scale, int is_bf16,
-                const int* kv_len, int n_heads, hipStream_t stream) {
+                int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
+                const int* kv_len, const int64_t* qkv_strides,
+                const int64_t* o_strides, hipStream_t stream) {
+  const dr::MhaStrides qs = dr::mha_strides(qkv_strides);
+  const dr::MhaStrides os = dr::mha_strides(o_strides);
   if (is_bf16)
-    dr::mha_fwd_launch_t<uint16_t>(q, k, v, o, lse, BH, T_len, D, scale, kv_len,
-                                   n_heads, stream);
+    dr::mha_fwd_launch_t<uint16_t>(q, k, v, o, lse, B, n_heads, T_len, D, scale,
+                                   kv_len, qs, os, stream);
   else
-    dr::mha_fwd_launch_t<float>(q, k, v, o, lse, BH, T_len, D, scale, kv_len,
-                                n_heads, stream);
+    dr::mha_fwd_launch_t<float>(q, k, v, o, lse, B, n_heads, T_len, D, scale,
+                                kv_len, qs, os, stream);
 }
 
 }  // extern "C"

@@ -74,13 +74,17 @@ int dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
                       void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
                       void* xg_pi, int64_t BT, int C, int mode, int is_bf16,
                       hipStream_t stream);
+// *_strides: {batch, head, time} element strides, d stride 1 (attention.hip)
+int dr_mha_bwd_writes_dq(int T_len, int D);
 void dr_mha_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
-                int64_t BH, int T_len, int D, float scale, int is_bf16,
-                const int* kv_len, int n_heads, hipStream_t stream);
+                int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
+                const int* kv_len, const int64_t* qkv_strides,
+                const int64_t* o_strides, hipStream_t stream);
 void dr_mha_bwd(const void* q, const void* k, const void* v, const void* o,
-                const void* dout, const float* lse, float* dq, void* dk, void* dv,
-                int64_t BH, int T_len, int D, float scale, int is_bf16,
-                hipStream_t stream);
+                const void* dout, const float* lse, void* dq, void* dk, void* dv,
+                int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
+                const int64_t* qkv_strides, const int64_t* o_strides,
+                const int64_t* dq_strides, hipStream_t stream);
 int dr_sanity_scores(const void* out, const float* measured, const float* base,
                      const float* y_min, const float* y_scale,
                      const float* conformal, const int* lengths, int64_t N,
@@ -712,6 +716,28 @@ std::vector<at::Tensor> gru_bwd_reduce(at::Tensor dpre, at::Tensor gamma,
 }
 
 // -------------------------------------------------------------------- mha
+// The kernels address (batch, head, time, d) operands by element strides.
+struct MhaLayout {
+  int64_t s[3];
+};
+// (B, H, T, D) contiguous
+static MhaLayout mha_bhtd(int64_t NH, int64_t T, int64_t D) {
+  return {{NH * T * D, T * D, D}};
+}
+// one of the three parts of a packed (B, T, 3, H, D) qkv
+static MhaLayout mha_packed_part(int64_t NH, int64_t T, int64_t D) {
+  return {{T * 3 * NH * D, D, 3 * NH * D}};
+}
+// (B, T, H, D) contiguous
+static MhaLayout mha_bthd(int64_t NH, int64_t T, int64_t D) {
+  return {{T * NH * D, D, NH * D}};
+}
+
+static void mha_check_head_dim(int64_t D) {
+  TORCH_CHECK(D >= 8 && D <= 64 && D % 8 == 0,
+              "head dim must be 8..64, mult of 8, got ", D);
+}
+
 // kv_lengths (optional, (B,) int32): keys >= kv_lengths[b] are absent and
 // rows of o / lse at or past it are zero (inference only; mha_backward does
 // not know about lengths).
@@ -724,7 +750,7 @@ std::vector<at::Tensor> mha_forward(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
   int64_t B = q.size(0), NH = q.size(1);
   int T_len = (int)q.size(2), D = (int)q.size(3);
-  TORCH_CHECK(D >= 8 && D <= 64 && D % 8 == 0, "head dim must be 8..64, mult of 8");
+  mha_check_head_dim(D);
   const int* kv_len = lengths_ptr(kv_lengths, q, B, "mha kv_lengths");
   if (kv_len != nullptr)
     TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes() &&
@@ -733,12 +759,15 @@ std::vector<at::Tensor> mha_forward(at::Tensor q, at::Tensor k, at::Tensor v,
                 "mha with kv_lengths: q, k, v must share shape and dtype");
   auto o = at::empty_like(q);
   auto lse = at::empty({B, NH, T_len}, q.options().dtype(at::kFloat));
+  const MhaLayout l = mha_bhtd(NH, T_len, D);
   dr_mha_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-             lse.data_ptr<float>(), B * NH, T_len, D, (float)scale,
-             is_bf16(q), kv_len, (int)NH, cur_stream());
+             lse.data_ptr<float>(), B, (int)NH, T_len, D, (float)scale,
+             is_bf16(q), kv_len, l.s, l.s, cur_stream());
   return {o, lse};
 }
 
+// dq comes back in q's dtype where the kernel writes it itself (one key tile
+// per head), as the fp32 atomic accumulator otherwise.
 std::vector<at::Tensor> mha_backward(at::Tensor q, at::Tensor k, at::Tensor v,
                                      at::Tensor o, at::Tensor dout, at::Tensor lse,
                                      double scale) {
@@ -746,14 +775,109 @@ std::vector<at::Tensor> mha_backward(at::Tensor q, at::Tensor k, at::Tensor v,
   int64_t B = q.size(0), NH = q.size(1);
   int T_len = (int)q.size(2), D = (int)q.size(3);
   TORCH_CHECK(dout.is_contiguous() && o.is_contiguous());
-  auto dq = at::zeros(q.sizes(), q.options().dtype(at::kFloat));
+  const bool writes_dq = dr_mha_bwd_writes_dq(T_len, D) != 0;
+  auto dq = writes_dq ? at::empty_like(q)
+                      : at::zeros(q.sizes(), q.options().dtype(at::kFloat));
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
+  const MhaLayout l = mha_bhtd(NH, T_len, D);
   dr_mha_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-             dout.data_ptr(), lse.data_ptr<float>(), dq.data_ptr<float>(),
-             dk.data_ptr(), dv.data_ptr(), B * NH, T_len, D, (float)scale,
-             is_bf16(q), cur_stream());
+             dout.data_ptr(), lse.data_ptr<float>(), dq.data_ptr(),
+             dk.data_ptr(), dv.data_ptr(), B, (int)NH, T_len, D, (float)scale,
+             is_bf16(q), l.s, l.s, l.s, cur_stream());
   return {dq, dk, dv};
+}
+
+// Attention on the packed qkv GEMM output: qkv (B, T, 3*H*Dh) or
+// (B, T, 3, H, Dh) contiguous -> {o (B, T, H*Dh), lse (B, H, T)}.  No copy of
+// q, k, v or o is made: the kernels take the row strides and the head offset.
+struct PackedShape {
+  int64_t B, T, NH, D;
+};
+
+static PackedShape mha_packed_checks(const at::Tensor& qkv, int64_t n_heads) {
+  check_dtype(qkv, "qkv");
+  TORCH_CHECK(qkv.is_cuda(), "qkv must be a GPU tensor");
+  TORCH_CHECK(qkv.is_contiguous(), "qkv must be contiguous");
+  TORCH_CHECK(n_heads >= 1, "n_heads must be >= 1, got ", n_heads);
+  TORCH_CHECK(qkv.dim() == 3 || qkv.dim() == 5,
+              "qkv must be (B, T, 3*H*Dh) or (B, T, 3, H, Dh)");
+  PackedShape s;
+  s.B = qkv.size(0);
+  s.T = qkv.size(1);
+  s.NH = n_heads;
+  if (qkv.dim() == 5) {
+    TORCH_CHECK(qkv.size(2) == 3 && qkv.size(3) == n_heads,
+                "qkv must be (B, T, 3, n_heads = ", n_heads, ", Dh), got ",
+                qkv.sizes());
+    s.D = qkv.size(4);
+  } else {
+    TORCH_CHECK(qkv.size(2) % (3 * n_heads) == 0,
+                "qkv's last dimension (", qkv.size(2), ") is not 3 * n_heads (",
+                n_heads, ") * Dh");
+    s.D = qkv.size(2) / (3 * n_heads);
+  }
+  mha_check_head_dim(s.D);
+  TORCH_CHECK(s.T >= 1 && s.T < (1LL << 31), "qkv needs 1 <= T < 2^31");
+  // every (t, part, head) row starts on a 16-byte boundary (Dh % 8 == 0)
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "qkv must be 16-byte aligned");
+  return s;
+}
+
+std::vector<at::Tensor> mha_packed_forward(at::Tensor qkv, int64_t n_heads,
+                                           double scale) {
+  const at::cuda::CUDAGuard guard(qkv.device());
+  const PackedShape s = mha_packed_checks(qkv, n_heads);
+  auto o = at::empty({s.B, s.T, s.NH * s.D}, qkv.options());
+  auto lse = at::empty({s.B, s.NH, s.T}, qkv.options().dtype(at::kFloat));
+  if (s.B == 0) return {o, lse};
+  const int64_t part = s.NH * s.D * qkv.element_size();
+  const char* base = static_cast<const char*>(qkv.data_ptr());
+  const MhaLayout ql = mha_packed_part(s.NH, s.T, s.D);
+  const MhaLayout ol = mha_bthd(s.NH, s.T, s.D);
+  dr_mha_fwd(base, base + part, base + 2 * part, o.data_ptr(),
+             lse.data_ptr<float>(), s.B, (int)s.NH, (int)s.T, (int)s.D,
+             (float)scale, is_bf16(qkv), nullptr, ql.s, ol.s, cur_stream());
+  return {o, lse};
+}
+
+// dout (B, T, H*Dh) contiguous -> dqkv (B, T, 3, H, Dh) in qkv's dtype, written
+// by the kernel in place of its q, k, v parts.
+at::Tensor mha_packed_backward(at::Tensor qkv, int64_t n_heads, at::Tensor o,
+                               at::Tensor dout, at::Tensor lse, double scale) {
+  const at::cuda::CUDAGuard guard(qkv.device());
+  const PackedShape s = mha_packed_checks(qkv, n_heads);
+  for (const at::Tensor* t : {&o, &dout})
+    TORCH_CHECK(t->is_cuda() && t->device() == qkv.device() &&
+                    t->scalar_type() == qkv.scalar_type() && t->is_contiguous() &&
+                    t->numel() == s.B * s.T * s.NH * s.D &&
+                    reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "o and dout must be contiguous (B, T, H*Dh) tensors of qkv's "
+                "dtype on its device, 16-byte aligned");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.device() == qkv.device() && lse.numel() == s.B * s.NH * s.T,
+              "lse must be the (B, H, T) f32 tensor of mha_packed_forward");
+  auto dqkv = at::empty({s.B, s.T, 3, s.NH, s.D}, qkv.options());
+  if (s.B == 0) return dqkv;
+  const int64_t part = s.NH * s.D * qkv.element_size();
+  const char* base = static_cast<const char*>(qkv.data_ptr());
+  char* dbase = static_cast<char*>(dqkv.data_ptr());
+  const MhaLayout ql = mha_packed_part(s.NH, s.T, s.D);
+  const MhaLayout ol = mha_bthd(s.NH, s.T, s.D);
+  // the fp32 atomic accumulator only where the launcher cannot prove one key
+  // tile per head
+  const bool writes_dq = dr_mha_bwd_writes_dq((int)s.T, (int)s.D) != 0;
+  at::Tensor dq32;
+  if (!writes_dq)
+    dq32 = at::zeros({s.B, s.T, s.NH, s.D}, qkv.options().dtype(at::kFloat));
+  dr_mha_bwd(base, base + part, base + 2 * part, o.data_ptr(), dout.data_ptr(),
+             lse.data_ptr<float>(), writes_dq ? (void*)dbase : dq32.data_ptr(),
+             dbase + part, dbase + 2 * part, s.B, (int)s.NH, (int)s.T, (int)s.D,
+             (float)scale, is_bf16(qkv), ql.s, ol.s, writes_dq ? ql.s : ol.s,
+             cur_stream());
+  if (!writes_dq) dqkv.select(2, 0).copy_(dq32);
+  return dqkv;
 }
 
 // ----------------------------------------------------------------- sanity
@@ -867,6 +991,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mha_forward", &mha_forward, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("scale"), py::arg("kv_lengths") = py::none());
   m.def("mha_backward", &mha_backward);
+  m.def("mha_packed_forward", &mha_packed_forward, py::arg("qkv"),
+        py::arg("n_heads"), py::arg("scale"));
+  m.def("mha_packed_backward", &mha_packed_backward, py::arg("qkv"),
+        py::arg("n_heads"), py::arg("o"), py::arg("dout"), py::arg("lse"),
+        py::arg("scale"));
   m.def("band_scores", &band_scores, py::arg("out"), py::arg("measured"),
         py::arg("y_min"), py::arg("y_scale"), py::arg("base") = py::none(),
         py::arg("conformal") = py::none(), py::arg("log1p") = false,

@@ -37,7 +37,7 @@ import torch.nn.functional as F
 from ..data.featurize import FeaturizedData
 from ..ops import (dropout_add, dropout_add_layer_norm, fused_gru_decode,
                    fused_gru_heads, fused_gru_sequence, layer_norm,
-                   masked_pinball_loss, mha_forward, pinball_loss)
+                   masked_pinball_loss, mha_forward, mha_packed, pinball_loss)
 from ..ops.gru import HEAD_FUSE_MAX_OUT, gru_kernel_supports
 from ..ops.linear_bigk import bigk_linear
 
@@ -205,14 +205,23 @@ class _EncoderLayer(nn.Module):
         self.n_heads = cfg.n_heads
         self.dropout = nn.Dropout(cfg.dropout)
 
+    def _attention(self, h: torch.Tensor,
+                   kv_lengths: Optional[torch.Tensor]) -> torch.Tensor:
+        """(B, T, D) normed input -> (B, T, D) attention output, before proj."""
+        if kv_lengths is None:
+            return mha_packed(self.qkv(h), self.n_heads)
+        # per-sample lengths (inference only): the (B, H, T, Dh) kernel
+        B, T, D = h.shape
+        qkv = self.qkv(h).view(B, T, 3, self.n_heads, D // self.n_heads)
+        q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # (B,h,T,dh)
+        attn = mha_forward(q, k, v, kv_lengths=kv_lengths)
+        return attn.transpose(1, 2).reshape(B, T, D)
+
     def forward(self, x: torch.Tensor,
                 kv_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, T, D = x.shape
         h = self.ln1(x)
-        qkv = self.qkv(h).view(B, T, 3, self.n_heads, D // self.n_heads)
-        q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # (B,h,T,dh)
-        attn = mha_forward(q, k, v, kv_lengths=kv_lengths)
-        attn = attn.transpose(1, 2).reshape(B, T, D)
+        attn = self._attention(h, kv_lengths)
         x = x + self.dropout(self.proj(attn))
         h = self.ln2(x)
         x = x + self.dropout(self.ff2(F.gelu(self.ff1(h))))
@@ -227,10 +236,7 @@ class _EncoderLayer(nn.Module):
         ``(x, next_ln(x))`` — the second entry is None for the last layer."""
         B, T, D = x.shape
         p, training = self.dropout.p, self.training
-        qkv = self.qkv(h).view(B, T, 3, self.n_heads, D // self.n_heads)
-        q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # (B,h,T,dh)
-        attn = mha_forward(q, k, v, kv_lengths=kv_lengths)
-        attn = attn.transpose(1, 2).reshape(B, T, D)
+        attn = self._attention(h, kv_lengths)
         x, h = dropout_add_layer_norm(self.proj(attn), x, self.ln2.weight,
                                       self.ln2.bias, p, training, self.ln2.eps)
         ff = self.ff2(F.gelu(self.ff1(h)))

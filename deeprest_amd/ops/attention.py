@@ -2,18 +2,29 @@
 
 The traffic encoder attends over the time axis of the encoded endpoint
 window (north star: "multi-head attention over the endpoint x time window on
-MFMA with LDS-staged tiles").  The forward is ONE fused HIP kernel per
-(batch, head): QK^T on MFMA with K staged in LDS (XOR-swizzled), online
-softmax in registers, PV on MFMA — no S x S score tensor is materialized.
-It saves the per-row logsumexp so the backward can recompute P cheaply.
+MFMA with LDS-staged tiles").  Two entry points share one set of kernels
+(``csrc/attention.hip``), which address their operands by (batch, head,
+time) element strides:
 
-The backward is ONE fused kernel per (batch-head, 64-key tile) in a
-TRANSPOSED layout — keys as MFMA rows, queries as columns — so S^T, dP^T and
-dS^T share one C-fragment layout and the softmax-grad math is lane-local
-(per-column lse and D-row); dK/dV accumulate in registers with exclusive
-stores, dQ via fp32 atomics.  It recomputes P from the saved logsumexp
-instead of storing the S x S score tensor (replaced a rocBLAS recompute-GEMM
-chain: 1 ms -> 0.23 ms per step at the bench config).
+``mha_packed(qkv, n_heads)`` is what the model calls.  It takes the qkv GEMM
+output ``(B, T, 3*H*Dh)`` as it is and returns ``(B, T, H*Dh)``, the layout
+the output projection reads: no copy of q, k, v or o, and one autograd node
+whose backward writes a single ``(B, T, 3, H, Dh)`` dqkv.
+
+``mha_forward(q, k, v)`` takes ``(B, H, T, D)`` contiguous tensors, and is
+the only path with per-sample ``kv_lengths`` (inference).
+
+Kernels.  With T <= 64 and Dh in {16, 32, 64} one wave holds a whole (batch,
+head): every global access is a 16-byte piece of a (t, head) row, the softmax
+is taken once over all keys, the probability accumulators are the next MFMA's
+operand, transposed operands come from ``ds_read_b64_tr_b16`` on row-major LDS
+images, and there is no block barrier.  The backward recomputes P from the
+saved per-row logsumexp and writes dq, dk, dv itself in the IO dtype: no
+atomics, so the result is deterministic.  Longer windows (and other head
+sizes) run the flash-style bodies: one workgroup per 64-row query tile with an
+online softmax forward, one per (head, 64-key tile) backward in a transposed
+layout whose dQ contributions go out as fp32 atomics into a zeroed buffer.
+No S x S score tensor is ever materialized.
 
 Replaces and upgrades the reference's per-metric feature-mask "attention"
 (reference: resource-estimation/qrnn.py:21-23,34).
@@ -27,6 +38,11 @@ from typing import Optional
 import torch
 
 from .native import require_native
+
+# "auto": mha_packed runs the strided kernels on the packed tensor (GPU).
+# "off": it runs the composition of views, mha_forward and the transposing
+# reshape, as the CPU path always does.  For tests and tools.
+PACKED_MODE = "auto"
 
 
 def reference_mha(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -99,3 +115,56 @@ def mha_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if q.is_cuda:
         return _MHAFunction.apply(q.contiguous(), k.contiguous(), v.contiguous(), scale)
     return reference_mha(q, k, v, scale)
+
+
+class _MHAPackedFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, n_heads, scale):
+        ext = require_native("mha_packed_forward")
+        o, lse = ext.mha_packed_forward(qkv, int(n_heads), float(scale))
+        ctx.save_for_backward(qkv, o, lse)
+        ctx.n_heads = int(n_heads)
+        ctx.scale = float(scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, grad_o):
+        ext = require_native("mha_packed_backward")
+        qkv, o, lse = ctx.saved_tensors
+        grad_o = grad_o.contiguous()
+        if grad_o.data_ptr() % 16:          # a view at an odd offset
+            grad_o = grad_o.clone()
+        dqkv = ext.mha_packed_backward(qkv, ctx.n_heads, o, grad_o, lse, ctx.scale)
+        return dqkv.view(qkv.shape), None, None
+
+
+def _mha_unpacked(qkv: torch.Tensor, n_heads: int,
+                  scale: Optional[float]) -> torch.Tensor:
+    B, T = qkv.shape[0], qkv.shape[1]
+    qkv5 = qkv.view(B, T, 3, n_heads, -1)
+    q, k, v = (qkv5[:, :, i].transpose(1, 2) for i in range(3))    # (B,h,T,dh)
+    attn = mha_forward(q, k, v, scale)
+    return attn.transpose(1, 2).reshape(B, T, -1)
+
+
+def mha_packed(qkv: torch.Tensor, n_heads: int,
+               scale: Optional[float] = None) -> torch.Tensor:
+    """Attention on the packed qkv projection.
+
+    ``qkv``: ``(B, T, 3*H*Dh)`` or ``(B, T, 3, H, Dh)`` contiguous, bf16 or
+    f32, Dh a multiple of 8 in 8..64 on the GPU; returns ``(B, T, H*Dh)``
+    contiguous.  On the GPU the kernels read q, k, v in place and write the
+    output and, in the backward, one dqkv tensor directly; a bad operand
+    raises before any launch.  On the CPU, and with ``PACKED_MODE = "off"``,
+    it is the composition of the three views, ``mha_forward`` and the
+    transposing reshape."""
+    if PACKED_MODE not in ("auto", "off"):
+        raise ValueError(f"PACKED_MODE must be 'auto' or 'off', got {PACKED_MODE!r}")
+    if qkv.is_cuda and PACKED_MODE == "auto":
+        if qkv.dim() not in (3, 5):
+            raise RuntimeError("qkv must be (B, T, 3*H*Dh) or (B, T, 3, H, Dh)")
+        if scale is None:
+            last = qkv.shape[-1] if qkv.dim() == 5 else qkv.shape[-1] // (3 * n_heads)
+            scale = 1.0 / math.sqrt(max(last, 1))
+        return _MHAPackedFunction.apply(qkv, n_heads, scale)
+    return _mha_unpacked(qkv, n_heads, scale)
