@@ -40,7 +40,7 @@ void dr_pinball_masked_bwd(const void* out, const float* labels,
                            const float* grad_loss, const float* w, void* dout,
                            int is_bf16, hipStream_t stream);
 void dr_fused_adam(const int64_t* meta, int nt, int64_t total, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int step,
+                   float beta2, float eps, float weight_decay, int64_t step,
                    hipStream_t stream);
 void dr_fused_adam_dev(const int64_t* meta, int nt, int64_t total,
                        const float* lr_ptr, float beta1, float beta2, float eps,
@@ -389,28 +389,48 @@ at::Tensor pinball_masked_backward(at::Tensor grad, at::Tensor outputs,
 // ------------------------------------------------------------- fused adam
 void fused_adam(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                 std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
-                int64_t step, double lr, double beta1, double beta2, double eps,
-                double weight_decay) {
+                std::vector<int64_t> steps, double lr, double beta1, double beta2,
+                double eps, double weight_decay) {
   TORCH_CHECK(!params.empty());
+  TORCH_CHECK(params[0].is_cuda(), "fused_adam expects device tensors");
   const at::cuda::CUDAGuard guard(params[0].device());
   int nt = (int)params.size();
-  std::vector<int64_t> meta(5 * nt);
+  TORCH_CHECK(grads.size() == params.size() && ms.size() == params.size() &&
+                  vs.size() == params.size() && steps.size() == params.size(),
+              "fused_adam: params, grads, exp_avgs, exp_avg_sqs and steps differ in length");
+  std::vector<int64_t> meta(6 * nt);
   int64_t total = 0;
   for (int i = 0; i < nt; ++i) {
-    TORCH_CHECK(params[i].scalar_type() == at::kFloat, "fused_adam expects f32 params");
-    TORCH_CHECK(params[i].is_contiguous() && grads[i].is_contiguous());
+    const at::Tensor* ops[4] = {&params[i], &grads[i], &ms[i], &vs[i]};
+    static const char* names[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
+    for (int o = 0; o < 4; ++o) {
+      const at::Tensor& t = *ops[o];
+      TORCH_CHECK(t.scalar_type() == at::kFloat, "fused_adam expects f32 ", names[o],
+                  " (tensor ", i, ")");
+      TORCH_CHECK(t.is_contiguous(), "fused_adam expects contiguous ", names[o],
+                  " (tensor ", i, ")");
+      TORCH_CHECK(t.device() == params[0].device(), "fused_adam: ", names[o],
+                  " of tensor ", i, " is on another device");
+      TORCH_CHECK(t.numel() == params[i].numel(), "fused_adam: ", names[o],
+                  " of tensor ", i, " has ", t.numel(), " elements, param has ",
+                  params[i].numel());
+    }
+    TORCH_CHECK(steps[i] >= 1, "fused_adam: step of tensor ", i, " must be >= 1");
     meta[i] = (int64_t)params[i].data_ptr();
     meta[nt + i] = (int64_t)grads[i].data_ptr();
     meta[2 * nt + i] = (int64_t)ms[i].data_ptr();
     meta[3 * nt + i] = (int64_t)vs[i].data_ptr();
     total += params[i].numel();
     meta[4 * nt + i] = total;  // cumulative end offsets
+    meta[5 * nt + i] = steps[i];  // the tensor's own step (bias correction)
   }
   auto meta_t = at::from_blob(meta.data(), {(int64_t)meta.size()},
                               at::TensorOptions().dtype(at::kLong))
                     .to(params[0].device(), /*non_blocking=*/false);
+  // bias factors for steps[0] come from the host; a thread recomputes them
+  // only where a tensor's step differs
   dr_fused_adam(meta_t.data_ptr<int64_t>(), nt, total, (float)lr, (float)beta1,
-                (float)beta2, (float)eps, (float)weight_decay, (int)step,
+                (float)beta2, (float)eps, (float)weight_decay, steps[0],
                 cur_stream());
 }
 
@@ -424,6 +444,9 @@ void fused_adam_capturable(at::Tensor meta_dev, int64_t nt, int64_t total,
   const at::cuda::CUDAGuard guard(meta_dev.device());
   TORCH_CHECK(meta_dev.is_cuda() && meta_dev.scalar_type() == at::kLong &&
               meta_dev.is_contiguous());
+  TORCH_CHECK(nt >= 1 && meta_dev.numel() == 6 * nt,
+              "fused_adam_capturable: table must hold 6 entries per tensor "
+              "(p, g, m, v, cumulative numel, step lag)");
   TORCH_CHECK(step_t.is_cuda() && step_t.scalar_type() == at::kInt &&
               step_t.numel() == 1);
   TORCH_CHECK(lr_t.is_cuda() && lr_t.scalar_type() == at::kFloat &&

@@ -21,7 +21,7 @@ from .residual_norm import (dropout_add, dropout_add_layer_norm, philox_keep_mas
 from .attention import mha_forward, mha_packed, reference_mha
 from .pinball import (masked_pinball_loss, pinball_loss,
                       reference_masked_pinball_loss, reference_pinball_loss)
-from .adam import fused_adam_step
+from .adam import fused_adam_step, reference_adam_step
 from .sanity import BandScores, band_scores, reference_band_scores
 
 __all__ = [
@@ -46,6 +46,7 @@ __all__ = [
     "masked_pinball_loss",
     "reference_masked_pinball_loss",
     "fused_adam_step",
+    "reference_adam_step",
     "BandScores",
     "band_scores",
     "reference_band_scores",
