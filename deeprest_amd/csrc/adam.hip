@@ -10,6 +10,7 @@
 // with k the tensor's OWN step count (torch.optim.Adam keeps one per
 // parameter: a parameter whose gradients start late is at a lower k).
 #include "common.h"
+#include "kernels.h"
 
 namespace dr {
 
@@ -95,33 +96,34 @@ __global__ void fused_adam_kernel(const int64_t* __restrict__ meta, int nt,
   }
 }
 
-}  // namespace dr
-
-extern "C" {
-
-void dr_fused_adam(const int64_t* meta, int nt, int64_t total, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int64_t step,
-                   hipStream_t stream) {
-  const int block = 256;
-  int grid = (int)std::min<int64_t>((total + block - 1) / block, 4096);
-  if (grid == 0) grid = 1;
-  float bias_c1 = 1.f - powf(beta1, (float)step);
-  float bias_c2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL((dr::fused_adam_kernel<false>), dim3(grid), dim3(block), 0,
-                     stream, meta, nt, total, lr, beta1, beta2, eps, weight_decay,
-                     bias_c1, bias_c2, step, nullptr, nullptr);
+// grid-stride over all elements, at least one block
+static dim3 adam_grid(int64_t total) {
+  return dim3((unsigned)std::max<int64_t>(std::min<int64_t>((total + 255) / 256, 4096), 1));
 }
 
-void dr_fused_adam_dev(const int64_t* meta, int nt, int64_t total,
-                       const float* lr_ptr, float beta1, float beta2, float eps,
-                       float weight_decay, const int* step_ptr,
-                       hipStream_t stream) {
-  const int block = 256;
-  int grid = (int)std::min<int64_t>((total + block - 1) / block, 4096);
-  if (grid == 0) grid = 1;
-  hipLaunchKernelGGL((dr::fused_adam_kernel<true>), dim3(grid), dim3(block), 0,
-                     stream, meta, nt, total, 0.f, beta1, beta2, eps, weight_decay,
+}  // namespace dr
+
+// Entry contracts: kernels.h.
+extern "C" {
+
+int dr_fused_adam(const int64_t* meta, int nt, int64_t total, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int64_t step,
+                  hipStream_t stream) {
+  float bias_c1 = 1.f - powf(beta1, (float)step);
+  float bias_c2 = 1.f - powf(beta2, (float)step);
+  hipLaunchKernelGGL((dr::fused_adam_kernel<false>), dr::adam_grid(total), dim3(256),
+                     0, stream, meta, nt, total, lr, beta1, beta2, eps, weight_decay,
+                     bias_c1, bias_c2, step, nullptr, nullptr);
+  return (int)hipGetLastError();
+}
+
+int dr_fused_adam_dev(const int64_t* meta, int nt, int64_t total,
+                      const float* lr_ptr, float beta1, float beta2, float eps,
+                      float weight_decay, const int* step_ptr, hipStream_t stream) {
+  hipLaunchKernelGGL((dr::fused_adam_kernel<true>), dr::adam_grid(total), dim3(256),
+                     0, stream, meta, nt, total, 0.f, beta1, beta2, eps, weight_decay,
                      0.f, 0.f, (int64_t)0, step_ptr, lr_ptr);
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

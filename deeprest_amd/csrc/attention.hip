@@ -20,6 +20,8 @@
 // Head dims supported: 8 <= D <= 64, D % 8 == 0 (the traffic encoder uses
 // D = d_model / n_heads = 32).
 #include "common.h"
+#include "kernels.h"
+#include "launch.h"
 
 namespace dr {
 
@@ -959,105 +961,98 @@ static bool mha_whole_tile(int T_len, int D) {
   return T_len >= 1 && T_len <= TILE_T && (D == 16 || D == 32 || D == 64);
 }
 
-template <typename T>
-static void mha_fwd_launch_t(const void* q, const void* k, const void* v, void* o,
-                             float* lse, int64_t B, int n_heads, int T_len, int D,
-                             float scale, const int* kv_len, MhaStrides qs,
-                             MhaStrides os, hipStream_t stream) {
-  const int64_t BH = B * n_heads;
-  if (kv_len == nullptr && mha_whole_tile(T_len, D)) {
-    dim3 grid((unsigned)((BH + A_WAVES - 1) / A_WAVES));
-#define DR_MHA_TILE_FWD(DH_)                                                     \
-  hipLaunchKernelGGL((mha_tile_fwd_kernel<T, DH_>), grid, dim3(A_THREADS), 0,    \
-                     stream, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse,  \
-                     qs, os, BH, n_heads, T_len, scale)
-    if (D == 16) DR_MHA_TILE_FWD(16);
-    else if (D == 32) DR_MHA_TILE_FWD(32);
-    else DR_MHA_TILE_FWD(64);
-#undef DR_MHA_TILE_FWD
-    return;
-  }
-  dim3 grid((T_len + QT - 1) / QT, (unsigned)BH);
-  if (kv_len != nullptr)
-    hipLaunchKernelGGL((mha_fwd_kernel<T, true>), grid, dim3(A_THREADS), 0,
-                       stream, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse,
-                       qs, os, T_len, D, scale, kv_len, n_heads);
-  else
-    hipLaunchKernelGGL((mha_fwd_kernel<T, false>), grid, dim3(A_THREADS), 0,
-                       stream, (const T*)q, (const T*)k, (const T*)v, (T*)o, lse,
-                       qs, os, T_len, D, scale, nullptr, n_heads);
+// run f with the head dim of the whole-head tile kernels as a tag
+template <typename F>
+static hipError_t with_tile_dh(int D, F&& f) {
+  if (D == 16) return f(std::integral_constant<int, 16>{});
+  if (D == 32) return f(std::integral_constant<int, 32>{});
+  return f(std::integral_constant<int, 64>{});
 }
 
 template <typename T>
-static void mha_bwd_launch_t(const void* q, const void* k, const void* v,
-                             const void* o, const void* dout, const float* lse,
-                             void* dq, void* dk, void* dv, int64_t B, int n_heads,
-                             int T_len, int D, float scale, MhaStrides qs,
-                             MhaStrides os, MhaStrides dqs, hipStream_t stream) {
+static hipError_t mha_fwd_launch(const void* q, const void* k, const void* v,
+                                 void* o, float* lse, int64_t B, int n_heads,
+                                 int T_len, int D, float scale, const int* kv_len,
+                                 MhaStrides qs, MhaStrides os, hipStream_t stream) {
+  const int64_t BH = B * n_heads;
+  if (kv_len == nullptr && mha_whole_tile(T_len, D)) {
+    dim3 grid((unsigned)((BH + A_WAVES - 1) / A_WAVES));
+    return with_tile_dh(D, [&](auto dh) {
+      hipLaunchKernelGGL((mha_tile_fwd_kernel<T, decltype(dh)::value>), grid,
+                         dim3(A_THREADS), 0, stream, (const T*)q, (const T*)k,
+                         (const T*)v, (T*)o, lse, qs, os, BH, n_heads, T_len,
+                         scale);
+      return hipGetLastError();
+    });
+  }
+  dim3 grid((T_len + QT - 1) / QT, (unsigned)BH);
+  auto flash = [&](auto varlen) {
+    hipLaunchKernelGGL((mha_fwd_kernel<T, decltype(varlen)::value>), grid,
+                       dim3(A_THREADS), 0, stream, (const T*)q, (const T*)k,
+                       (const T*)v, (T*)o, lse, qs, os, T_len, D, scale, kv_len,
+                       n_heads);
+    return hipGetLastError();
+  };
+  return kv_len != nullptr ? flash(std::true_type{}) : flash(std::false_type{});
+}
+
+template <typename T>
+static hipError_t mha_bwd_launch(const void* q, const void* k, const void* v,
+                                 const void* o, const void* dout, const float* lse,
+                                 void* dq, void* dk, void* dv, int64_t B,
+                                 int n_heads, int T_len, int D, float scale,
+                                 MhaStrides qs, MhaStrides os, MhaStrides dqs,
+                                 hipStream_t stream) {
   const int64_t BH = B * n_heads;
   if (mha_whole_tile(T_len, D)) {
     dim3 grid((unsigned)((BH + A_WAVES - 1) / A_WAVES));
-#define DR_MHA_TILE_BWD(DH_)                                                     \
-  hipLaunchKernelGGL((mha_tile_bwd_kernel<T, DH_>), grid, dim3(A_THREADS), 0,    \
-                     stream, (const T*)q, (const T*)k, (const T*)v, (const T*)o, \
-                     (const T*)dout, lse, (T*)dq, (T*)dk, (T*)dv, qs, os, BH,    \
-                     n_heads, T_len, scale)
-    if (D == 16) DR_MHA_TILE_BWD(16);
-    else if (D == 32) DR_MHA_TILE_BWD(32);
-    else DR_MHA_TILE_BWD(64);
-#undef DR_MHA_TILE_BWD
-    return;
+    return with_tile_dh(D, [&](auto dh) {
+      hipLaunchKernelGGL((mha_tile_bwd_kernel<T, decltype(dh)::value>), grid,
+                         dim3(A_THREADS), 0, stream, (const T*)q, (const T*)k,
+                         (const T*)v, (const T*)o, (const T*)dout, lse, (T*)dq,
+                         (T*)dk, (T*)dv, qs, os, BH, n_heads, T_len, scale);
+      return hipGetLastError();
+    });
   }
   dim3 grid((T_len + 63) / 64, (unsigned)BH);
   hipLaunchKernelGGL((mha_bwd_kernel<T>), grid, dim3(A_THREADS), 0, stream,
                      (const T*)q, (const T*)k, (const T*)v, (const T*)o,
                      (const T*)dout, lse, (float*)dq, (T*)dk, (T*)dv, qs, os, dqs,
                      T_len, D, scale, n_heads);
+  return hipGetLastError();
 }
 
 static MhaStrides mha_strides(const int64_t* s) { return MhaStrides{s[0], s[1], s[2]}; }
 
 }  // namespace dr
 
+// Entry contracts: kernels.h.
 extern "C" {
 
-// 1: dr_mha_bwd at these sizes writes dq itself, in the IO dtype and with the
-// q strides (no atomics); 0: it accumulates into a zeroed fp32 dq with the
-// strides dq_strides.
 int dr_mha_bwd_writes_dq(int T_len, int D) { return dr::mha_whole_tile(T_len, D) ? 1 : 0; }
 
-// *_strides: {batch, head, time} element strides (MhaStrides); q, k, v, dk, dv
-// (and a dq written in the IO dtype) share qkv_strides, o and dout o_strides.
-void dr_mha_bwd(const void* q, const void* k, const void* v, const void* o,
-                const void* dout, const float* lse, void* dq, void* dk, void* dv,
-                int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
-                const int64_t* qkv_strides, const int64_t* o_strides,
-                const int64_t* dq_strides, hipStream_t stream) {
-  const dr::MhaStrides qs = dr::mha_strides(qkv_strides);
-  const dr::MhaStrides os = dr::mha_strides(o_strides);
-  const dr::MhaStrides dqs = dr::mha_strides(dq_strides);
-  if (is_bf16)
-    dr::mha_bwd_launch_t<uint16_t>(q, k, v, o, dout, lse, dq, dk, dv, B, n_heads,
-                                   T_len, D, scale, qs, os, dqs, stream);
-  else
-    dr::mha_bwd_launch_t<float>(q, k, v, o, dout, lse, dq, dk, dv, B, n_heads,
-                                T_len, D, scale, qs, os, dqs, stream);
+int dr_mha_bwd(const void* q, const void* k, const void* v, const void* o,
+               const void* dout, const float* lse, void* dq, void* dk, void* dv,
+               int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
+               const int64_t* qkv_strides, const int64_t* o_strides,
+               const int64_t* dq_strides, hipStream_t stream) {
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    return dr::mha_bwd_launch<typename decltype(io)::type>(
+        q, k, v, o, dout, lse, dq, dk, dv, B, n_heads, T_len, D, scale,
+        dr::mha_strides(qkv_strides), dr::mha_strides(o_strides),
+        dr::mha_strides(dq_strides), stream);
+  });
 }
 
-// kv_len == nullptr: every sample is T_len long (the training kernels).
-// Otherwise (B,) int32 per-sample lengths on the device.
-void dr_mha_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
-                int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
-                const int* kv_len, const int64_t* qkv_strides,
-                const int64_t* o_strides, hipStream_t stream) {
-  const dr::MhaStrides qs = dr::mha_strides(qkv_strides);
-  const dr::MhaStrides os = dr::mha_strides(o_strides);
-  if (is_bf16)
-    dr::mha_fwd_launch_t<uint16_t>(q, k, v, o, lse, B, n_heads, T_len, D, scale,
-                                   kv_len, qs, os, stream);
-  else
-    dr::mha_fwd_launch_t<float>(q, k, v, o, lse, B, n_heads, T_len, D, scale,
-                                kv_len, qs, os, stream);
+int dr_mha_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
+               int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
+               const int* kv_len, const int64_t* qkv_strides,
+               const int64_t* o_strides, hipStream_t stream) {
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    return dr::mha_fwd_launch<typename decltype(io)::type>(
+        q, k, v, o, lse, B, n_heads, T_len, D, scale, kv_len,
+        dr::mha_strides(qkv_strides), dr::mha_strides(o_strides), stream);
+  });
 }
 
 }  // extern "C"

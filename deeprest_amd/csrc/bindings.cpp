@@ -1,7 +1,10 @@
 // Python bindings for the deeprest_amd CDNA4 kernels (torch extension).
 //
 // Tensor checking / allocation / stream plumbing lives here; the kernels in
-// *.hip are torch-free and exposed through a C ABI.
+// *.hip are torch-free and exposed through a C ABI (kernels.h).  No tensor's
+// data_ptr reaches an entry before it has been checked for device, dtype,
+// contiguity and the element count the kernel will index: a bad operand is an
+// exception before any launch, a refused launch an exception after it.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <c10/cuda/CUDAGuard.h>
@@ -11,88 +14,7 @@
 #include <string>
 #include <vector>
 
-// ---- C ABI launchers from the .hip translation units ----
-extern "C" {
-void dr_dropout_add_ln_fwd(const void* branch, const void* residual, const float* w,
-                           const float* b, const int64_t* seed, uint32_t thr,
-                           float scale, void* r_out, void* normed, float* mean,
-                           float* rstd, int64_t n_rows, int D, float eps,
-                           int is_bf16, hipStream_t stream);
-void dr_dropout_add_ln_bwd(const void* d_normed, const void* d_r_out,
-                           const void* r_out, const float* w, const float* mean,
-                           const float* rstd, const int64_t* seed, uint32_t thr,
-                           float scale, void* d_res, void* d_branch,
-                           float* dwdb_part, int n_blocks, int64_t n_rows, int D,
-                           int is_bf16, hipStream_t stream);
-void dr_pinball_fwd(const void* out, const float* labels, const float* quantiles,
-                    int Q, int64_t N, float inv_count, float* loss, int is_bf16,
-                    hipStream_t stream);
-void dr_pinball_bwd(const void* out, const float* labels, const float* quantiles,
-                    int Q, int64_t N, const float* grad_loss, float inv_n,
-                    void* dout, int is_bf16, hipStream_t stream);
-int dr_pinball_masked_slots(int M);
-void dr_pinball_masked_fwd(const void* out, const float* labels,
-                           const float* quantiles, int Q, int64_t R, int M,
-                           float* wsum, int* wcnt, float* loss, float* w,
-                           int is_bf16, hipStream_t stream);
-void dr_pinball_masked_bwd(const void* out, const float* labels,
-                           const float* quantiles, int Q, int64_t R, int M,
-                           const float* grad_loss, const float* w, void* dout,
-                           int is_bf16, hipStream_t stream);
-void dr_fused_adam(const int64_t* meta, int nt, int64_t total, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int64_t step,
-                   hipStream_t stream);
-void dr_fused_adam_dev(const int64_t* meta, int nt, int64_t total,
-                       const float* lr_ptr, float beta1, float beta2, float eps,
-                       float weight_decay, const int* step_ptr,
-                       hipStream_t stream);
-// the dr_gru_* entries return the HIP error of their set-up or launches, 0 on
-// success (gru_launch_check below)
-int dr_gru_fwd_fuses_heads(int B, int C);
-// `images`: dr_gru_operand_images_bytes(C, is_bf16) bytes of device memory in
-// which the entries build the pi-ordered gamma / beta / b_hh images that their
-// streaming kernel variants read (gamma / beta / b_hh stay natural-layout)
-int64_t dr_gru_operand_images_bytes(int C, int is_bf16);
-int dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
-               const void* w_hh, const float* b_hh, const void* h0, void* h_all,
-               void* saves, const void* wh_fwd, void* out, int O, int B, int TT,
-               int C, int reverse, int save, int fp8, int is_bf16, void* images,
-               hipStream_t stream);
-int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
-                  const void* w_hh, const float* b_hh, const void* h0,
-                  const void* wh_fwd, void* out, void* h_last, int B, int TT,
-                  int C, int O, int reverse, int fp8, int is_bf16,
-                  const int* lens, void* images, hipStream_t stream);
-int dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
-               const void* w_fwd, const void* xg, const void* gamma,
-               const void* beta, const float* b_hh, const void* h0,
-               const void* h_all, const void* saves, void* dpre, float* dh0,
-               int B, int TT, int C, int reverse, int is_bf16, void* images,
-               hipStream_t stream);
-int dr_gru_reduce_fused_max_c();
-int dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
-                      void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
-                      void* xg_pi, int64_t BT, int C, int mode, int is_bf16,
-                      hipStream_t stream);
-// *_strides: {batch, head, time} element strides, d stride 1 (attention.hip)
-int dr_mha_bwd_writes_dq(int T_len, int D);
-void dr_mha_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
-                int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
-                const int* kv_len, const int64_t* qkv_strides,
-                const int64_t* o_strides, hipStream_t stream);
-void dr_mha_bwd(const void* q, const void* k, const void* v, const void* o,
-                const void* dout, const float* lse, void* dq, void* dk, void* dv,
-                int64_t B, int n_heads, int T_len, int D, float scale, int is_bf16,
-                const int64_t* qkv_strides, const int64_t* o_strides,
-                const int64_t* dq_strides, hipStream_t stream);
-int dr_sanity_scores(const void* out, const float* measured, const float* base,
-                     const float* y_min, const float* y_scale,
-                     const float* conformal, const int* lengths, int64_t N,
-                     int TT, int M, int log1p, float threshold, int min_run,
-                     float* scores, uint8_t* flags, float* max_score,
-                     int* n_flagged, int* first_flag, int* n_observed,
-                     float* bands, int is_bf16, hipStream_t stream);
-}
+#include "kernels.h"
 
 namespace {
 
@@ -105,6 +27,34 @@ void check_dtype(const at::Tensor& t, const char* name) {
 
 hipStream_t cur_stream() {
   return at::cuda::getCurrentCUDAStream().stream();
+}
+
+// a kernel entry's return value: a rejected set-up or launch is the caller's
+// error, never a silently wrong result
+void launch_check(int err, const char* entry) {
+  TORCH_CHECK(err == 0, entry, " failed (HIP error ", err, ": ",
+              hipGetErrorString((hipError_t)err), ")");
+}
+
+// operand `t`: on ref's GPU, of dtype dt, contiguous, with numel elements
+void check_operand(const at::Tensor& t, const char* name, const at::Tensor& ref,
+                   at::ScalarType dt, int64_t numel) {
+  TORCH_CHECK(ref.is_cuda() && t.device() == ref.device(), name,
+              " must be on the GPU of the call's first operand (", ref.device(),
+              "), got ", t.device());
+  TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt, ", got ",
+              t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.numel() == numel, name, " must have ", numel, " elements, got ",
+              t.numel());
+}
+
+// same, with exactly this shape
+void check_operand(const at::Tensor& t, const char* name, const at::Tensor& ref,
+                   at::ScalarType dt, at::IntArrayRef shape) {
+  TORCH_CHECK(t.sizes() == shape, name, " must have shape ", shape, ", got ",
+              t.sizes());
+  check_operand(t, name, ref, dt, t.numel());
 }
 
 // optional per-sample lengths of the inference kernels: (B,) int32 on the
@@ -166,10 +116,8 @@ std::vector<at::Tensor> dropout_add_ln_forward(c10::optional<at::Tensor> branch,
   const bool has_add = branch.has_value(), has_norm = w.has_value();
   TORCH_CHECK(b.has_value() == has_norm, "weight and bias go together");
   if (has_add) {
-    TORCH_CHECK(branch->device() == residual.device() && branch->is_contiguous());
-    TORCH_CHECK(branch->scalar_type() == residual.scalar_type() &&
-                    branch->sizes() == residual.sizes(),
-                "branch and residual must agree in dtype and shape");
+    check_operand(*branch, "branch", residual, residual.scalar_type(),
+                  residual.sizes());
   } else {
     TORCH_CHECK(has_norm && !seed.has_value(),
                 "without a branch the op is layer_norm: weight/bias, no seed");
@@ -181,11 +129,8 @@ std::vector<at::Tensor> dropout_add_ln_forward(c10::optional<at::Tensor> branch,
   auto f32 = residual.options().dtype(at::kFloat);
   at::Tensor normed, mean, rstd;
   if (has_norm) {
-    TORCH_CHECK(w->is_contiguous() && b->is_contiguous());
-    TORCH_CHECK(w->scalar_type() == at::kFloat && b->scalar_type() == at::kFloat,
-                "layer_norm weight/bias must be f32");
-    TORCH_CHECK(w->device() == residual.device() && b->device() == residual.device());
-    TORCH_CHECK(w->numel() == D && b->numel() == D);
+    check_operand(*w, "layer_norm weight", residual, at::kFloat, D);
+    check_operand(*b, "layer_norm bias", residual, at::kFloat, D);
     normed = at::empty_like(residual);
     mean = at::empty({n_rows}, f32);
     rstd = at::empty({n_rows}, f32);
@@ -195,14 +140,17 @@ std::vector<at::Tensor> dropout_add_ln_forward(c10::optional<at::Tensor> branch,
     rstd = at::empty({0}, f32);
   }
   if (n_rows > 0)
-    dr_dropout_add_ln_fwd(has_add ? branch->data_ptr() : nullptr, residual.data_ptr(),
-                          has_norm ? w->data_ptr<float>() : nullptr,
-                          has_norm ? b->data_ptr<float>() : nullptr, da.seed,
-                          da.thr, da.scale, has_add ? r_out.data_ptr() : nullptr,
-                          has_norm ? normed.data_ptr() : nullptr,
-                          has_norm ? mean.data_ptr<float>() : nullptr,
-                          has_norm ? rstd.data_ptr<float>() : nullptr, n_rows, D,
-                          (float)eps, is_bf16(residual), cur_stream());
+    launch_check(
+        dr_dropout_add_ln_fwd(
+            has_add ? branch->data_ptr() : nullptr, residual.data_ptr(),
+            has_norm ? w->data_ptr<float>() : nullptr,
+            has_norm ? b->data_ptr<float>() : nullptr, da.seed, da.thr, da.scale,
+            has_add ? r_out.data_ptr() : nullptr,
+            has_norm ? normed.data_ptr() : nullptr,
+            has_norm ? mean.data_ptr<float>() : nullptr,
+            has_norm ? rstd.data_ptr<float>() : nullptr, n_rows, D, (float)eps,
+            is_bf16(residual), cur_stream()),
+        "dr_dropout_add_ln_fwd");
   return {r_out, normed, mean, rstd};
 }
 
@@ -220,11 +168,11 @@ std::vector<at::Tensor> dropout_add_ln_backward(c10::optional<at::Tensor> d_norm
   const at::cuda::CUDAGuard guard(r_out.device());
   check_dtype(r_out, "r_out");
   TORCH_CHECK(r_out.is_cuda() && r_out.is_contiguous());
+  TORCH_CHECK(r_out.dim() >= 1 && r_out.size(-1) > 0);
+  const auto dt = r_out.scalar_type();
   const bool has_add = d_r_out.has_value(), has_norm = w.has_value();
   if (has_add) {
-    TORCH_CHECK(d_r_out->device() == r_out.device() && d_r_out->is_contiguous());
-    TORCH_CHECK(d_r_out->scalar_type() == r_out.scalar_type() &&
-                d_r_out->sizes() == r_out.sizes());
+    check_operand(*d_r_out, "d_r_out", r_out, dt, r_out.sizes());
   } else {
     TORCH_CHECK(has_norm && !seed.has_value(),
                 "without d_r_out the op is layer_norm: weight, no seed");
@@ -242,13 +190,10 @@ std::vector<at::Tensor> dropout_add_ln_backward(c10::optional<at::Tensor> d_norm
   if (n_blocks == 0) n_blocks = 1;
   at::Tensor d_res, part;
   if (has_norm) {
-    TORCH_CHECK(d_normed->is_contiguous() && w->is_contiguous() &&
-                mean->is_contiguous() && rstd->is_contiguous());
-    TORCH_CHECK(d_normed->scalar_type() == r_out.scalar_type() &&
-                d_normed->sizes() == r_out.sizes());
-    TORCH_CHECK(w->scalar_type() == at::kFloat && w->numel() == D);
-    TORCH_CHECK(mean->scalar_type() == at::kFloat && mean->numel() == n_rows &&
-                rstd->scalar_type() == at::kFloat && rstd->numel() == n_rows);
+    check_operand(*d_normed, "d_normed", r_out, dt, r_out.sizes());
+    check_operand(*w, "layer_norm weight", r_out, at::kFloat, D);
+    check_operand(*mean, "layer_norm mean", r_out, at::kFloat, n_rows);
+    check_operand(*rstd, "layer_norm rstd", r_out, at::kFloat, n_rows);
     // dw/db partials live in 2 * D floats of dynamic LDS per block
     TORCH_CHECK(D <= 8192, "layer_norm backward supports D <= 8192, got ", D);
     d_res = at::empty_like(r_out);
@@ -258,53 +203,71 @@ std::vector<at::Tensor> dropout_add_ln_backward(c10::optional<at::Tensor> d_norm
   }
   at::Tensor d_branch = has_mask ? at::empty_like(r_out) : d_res;
   if (n_rows > 0)
-    dr_dropout_add_ln_bwd(has_norm ? d_normed->data_ptr() : nullptr,
-                          has_add ? d_r_out->data_ptr() : nullptr, r_out.data_ptr(),
-                          has_norm ? w->data_ptr<float>() : nullptr,
-                          has_norm ? mean->data_ptr<float>() : nullptr,
-                          has_norm ? rstd->data_ptr<float>() : nullptr, da.seed,
-                          da.thr, da.scale, has_norm ? d_res.data_ptr() : nullptr,
-                          has_mask ? d_branch.data_ptr() : nullptr,
-                          has_norm ? part.data_ptr<float>() : nullptr, n_blocks,
-                          n_rows, D, is_bf16(r_out), cur_stream());
+    launch_check(
+        dr_dropout_add_ln_bwd(
+            has_norm ? d_normed->data_ptr() : nullptr,
+            has_add ? d_r_out->data_ptr() : nullptr, r_out.data_ptr(),
+            has_norm ? w->data_ptr<float>() : nullptr,
+            has_norm ? mean->data_ptr<float>() : nullptr,
+            has_norm ? rstd->data_ptr<float>() : nullptr, da.seed, da.thr,
+            da.scale, has_norm ? d_res.data_ptr() : nullptr,
+            has_mask ? d_branch.data_ptr() : nullptr,
+            has_norm ? part.data_ptr<float>() : nullptr, n_blocks, n_rows, D,
+            is_bf16(r_out), cur_stream()),
+        "dr_dropout_add_ln_bwd");
   if (!has_norm) return {d_res, d_branch, at::empty({0}, f32), at::empty({0}, f32)};
   auto sums = part.sum(0);  // (2, D)
   return {d_res, d_branch, sums[0], sums[1]};
 }
 
 // ---------------------------------------------------------------- pinball
+// outputs (..., Q), labels with one entry per output row (any rank), q (Q,)
+struct PinballShape {
+  int Q;
+  int64_t N;
+};
+
+static PinballShape pinball_checks(const at::Tensor& outputs,
+                                   const at::Tensor& labels, const at::Tensor& q) {
+  check_dtype(outputs, "pinball outputs");
+  TORCH_CHECK(outputs.is_cuda() && outputs.is_contiguous() && outputs.dim() >= 1,
+              "pinball outputs must be a contiguous (..., Q) GPU tensor");
+  PinballShape s;
+  s.Q = (int)outputs.size(-1);
+  TORCH_CHECK(s.Q >= 1 && s.Q <= 8, "pinball wants 1 to 8 quantiles, got ", s.Q);
+  s.N = outputs.numel() / s.Q;
+  check_operand(labels, "pinball labels", outputs, at::kFloat, s.N);
+  check_operand(q, "pinball quantiles", outputs, at::kFloat, s.Q);
+  return s;
+}
+
 at::Tensor pinball_forward(at::Tensor outputs, at::Tensor labels, at::Tensor q) {
   const at::cuda::CUDAGuard guard(outputs.device());
-  check_dtype(outputs, "pinball outputs");
-  TORCH_CHECK(labels.scalar_type() == at::kFloat, "pinball labels must be f32");
-  TORCH_CHECK(outputs.is_contiguous() && labels.is_contiguous());
-  int Q = (int)outputs.size(-1);
-  TORCH_CHECK(Q <= 8, "at most 8 quantiles");
-  int64_t N = outputs.numel() / Q;
-  TORCH_CHECK(labels.numel() == N);
+  const PinballShape s = pinball_checks(outputs, labels, q);
   auto loss = at::zeros({}, outputs.options().dtype(at::kFloat));
-  float inv_count = N > 0 ? 1.0f / (float)N : 0.f;
-  dr_pinball_fwd(outputs.data_ptr(), labels.data_ptr<float>(),
-                 q.data_ptr<float>(), Q, N, inv_count, loss.data_ptr<float>(),
-                 is_bf16(outputs), cur_stream());
+  float inv_count = s.N > 0 ? 1.0f / (float)s.N : 0.f;
+  launch_check(dr_pinball_fwd(outputs.data_ptr(), labels.data_ptr<float>(),
+                              q.data_ptr<float>(), s.Q, s.N, inv_count,
+                              loss.data_ptr<float>(), is_bf16(outputs),
+                              cur_stream()),
+               "dr_pinball_fwd");
   return loss;
 }
 
+// The upstream grad stays on the device (no .item() host sync: the kernel
+// reads it, so the whole loss backward is hipGraph-capturable).
 at::Tensor pinball_backward(at::Tensor grad, at::Tensor outputs, at::Tensor labels,
                             at::Tensor q) {
   const at::cuda::CUDAGuard guard(outputs.device());
-  int Q = (int)outputs.size(-1);
-  int64_t N = outputs.numel() / Q;
+  const PinballShape s = pinball_checks(outputs, labels, q);
+  check_operand(grad, "pinball grad", outputs, at::kFloat, 1);
   auto dout = at::empty_like(outputs);
-  // keep the upstream grad on-device (no .item() host sync — the kernel reads
-  // it, so the whole loss backward is hipGraph-capturable)
-  TORCH_CHECK(grad.is_cuda() && grad.scalar_type() == at::kFloat && grad.numel() == 1,
-              "pinball grad must be a scalar f32 CUDA tensor");
-  float inv_n = N > 0 ? 1.f / (float)N : 0.f;
-  auto gc = grad.contiguous();
-  dr_pinball_bwd(outputs.data_ptr(), labels.data_ptr<float>(),
-                 q.data_ptr<float>(), Q, N, gc.data_ptr<float>(), inv_n,
-                 dout.data_ptr(), is_bf16(outputs), cur_stream());
+  float inv_n = s.N > 0 ? 1.f / (float)s.N : 0.f;
+  launch_check(dr_pinball_bwd(outputs.data_ptr(), labels.data_ptr<float>(),
+                              q.data_ptr<float>(), s.Q, s.N,
+                              grad.data_ptr<float>(), inv_n, dout.data_ptr(),
+                              is_bf16(outputs), cur_stream()),
+               "dr_pinball_bwd");
   return dout;
 }
 
@@ -359,11 +322,13 @@ std::vector<at::Tensor> pinball_masked_forward(at::Tensor outputs, at::Tensor la
   const int64_t slots = dr_pinball_masked_slots(s.M);
   auto ws = at::zeros({2, slots, s.M}, outputs.options().dtype(at::kInt));
   int* cnt = ws.data_ptr<int>() + slots * s.M;
-  dr_pinball_masked_fwd(outputs.data_ptr(), labels.data_ptr<float>(),
-                        q.data_ptr<float>(), s.Q, s.R, s.M,
-                        reinterpret_cast<float*>(ws.data_ptr<int>()), cnt,
-                        loss.data_ptr<float>(), w.data_ptr<float>(),
-                        is_bf16(outputs), cur_stream());
+  launch_check(
+      dr_pinball_masked_fwd(outputs.data_ptr(), labels.data_ptr<float>(),
+                            q.data_ptr<float>(), s.Q, s.R, s.M,
+                            reinterpret_cast<float*>(ws.data_ptr<int>()), cnt,
+                            loss.data_ptr<float>(), w.data_ptr<float>(),
+                            is_bf16(outputs), cur_stream()),
+      "dr_pinball_masked_fwd");
   return {loss, w};
 }
 
@@ -371,18 +336,18 @@ at::Tensor pinball_masked_backward(at::Tensor grad, at::Tensor outputs,
                                    at::Tensor labels, at::Tensor q, at::Tensor w) {
   const at::cuda::CUDAGuard guard(outputs.device());
   const MaskedShape s = pinball_masked_checks(outputs, labels, q);
-  TORCH_CHECK(grad.is_cuda() && grad.scalar_type() == at::kFloat && grad.numel() == 1,
-              "pinball grad must be a scalar f32 CUDA tensor");
+  check_operand(grad, "pinball grad", outputs, at::kFloat, 1);
   TORCH_CHECK(w.scalar_type() == at::kFloat && w.is_contiguous() &&
                   w.device() == outputs.device() && w.numel() == s.M,
               "w must be the (M,) f32 weights of pinball_masked_forward");
   auto dout = at::empty_like(outputs);
   if (s.R == 0 || s.M == 0 || s.Q == 0) return dout;
-  auto gc = grad.contiguous();
-  dr_pinball_masked_bwd(outputs.data_ptr(), labels.data_ptr<float>(),
-                        q.data_ptr<float>(), s.Q, s.R, s.M, gc.data_ptr<float>(),
-                        w.data_ptr<float>(), dout.data_ptr(), is_bf16(outputs),
-                        cur_stream());
+  launch_check(
+      dr_pinball_masked_bwd(outputs.data_ptr(), labels.data_ptr<float>(),
+                            q.data_ptr<float>(), s.Q, s.R, s.M,
+                            grad.data_ptr<float>(), w.data_ptr<float>(),
+                            dout.data_ptr(), is_bf16(outputs), cur_stream()),
+      "dr_pinball_masked_bwd");
   return dout;
 }
 
@@ -429,9 +394,10 @@ void fused_adam(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                     .to(params[0].device(), /*non_blocking=*/false);
   // bias factors for steps[0] come from the host; a thread recomputes them
   // only where a tensor's step differs
-  dr_fused_adam(meta_t.data_ptr<int64_t>(), nt, total, (float)lr, (float)beta1,
-                (float)beta2, (float)eps, (float)weight_decay, steps[0],
-                cur_stream());
+  launch_check(dr_fused_adam(meta_t.data_ptr<int64_t>(), nt, total, (float)lr,
+                             (float)beta1, (float)beta2, (float)eps,
+                             (float)weight_decay, steps[0], cur_stream()),
+               "dr_fused_adam");
 }
 
 // hipGraph-capturable variant: the pointer table is prebuilt on device (ops/
@@ -447,24 +413,16 @@ void fused_adam_capturable(at::Tensor meta_dev, int64_t nt, int64_t total,
   TORCH_CHECK(nt >= 1 && meta_dev.numel() == 6 * nt,
               "fused_adam_capturable: table must hold 6 entries per tensor "
               "(p, g, m, v, cumulative numel, step lag)");
-  TORCH_CHECK(step_t.is_cuda() && step_t.scalar_type() == at::kInt &&
-              step_t.numel() == 1);
-  TORCH_CHECK(lr_t.is_cuda() && lr_t.scalar_type() == at::kFloat &&
-              lr_t.numel() == 1);
-  dr_fused_adam_dev(meta_dev.data_ptr<int64_t>(), (int)nt, total,
-                    lr_t.data_ptr<float>(), (float)beta1, (float)beta2,
-                    (float)eps, (float)weight_decay, step_t.data_ptr<int>(),
-                    cur_stream());
+  check_operand(step_t, "fused_adam step counter", meta_dev, at::kInt, 1);
+  check_operand(lr_t, "fused_adam lr", meta_dev, at::kFloat, 1);
+  launch_check(dr_fused_adam_dev(meta_dev.data_ptr<int64_t>(), (int)nt, total,
+                                 lr_t.data_ptr<float>(), (float)beta1,
+                                 (float)beta2, (float)eps, (float)weight_decay,
+                                 step_t.data_ptr<int>(), cur_stream()),
+               "dr_fused_adam_dev");
 }
 
 // -------------------------------------------------------------------- gru
-// a kernel entry's return value: a rejected set-up or launch is the caller's
-// error, never a silently wrong result
-static void gru_launch_check(int err, const char* what) {
-  TORCH_CHECK(err == 0, what, " kernel launch failed (HIP error ", err, ": ",
-              hipGetErrorString((hipError_t)err), ")");
-}
-
 // the GEMM streams a bf16 weight image from L2 whatever the IO dtype is
 static at::Tensor gru_w_gemm(const at::Tensor& w_hh) {
   return is_bf16(w_hh) ? w_hh : w_hh.to(at::kBFloat16);
@@ -556,7 +514,7 @@ std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
                    : at::empty({0}, xg.options());
   auto w_gemm = gru_w_gemm(w_hh);
   auto images = gru_operand_images(gamma, C);
-  gru_launch_check(
+  launch_check(
       dr_gru_fwd(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                  w_gemm.data_ptr(), b_hh.data_ptr<float>(), h0.data_ptr(),
                  h_all.data_ptr(), save ? saves.data_ptr() : nullptr,
@@ -564,7 +522,7 @@ std::vector<at::Tensor> gru_seq_forward(at::Tensor xg, at::Tensor w_hh,
                  heads ? out.data_ptr() : nullptr, heads ? (int)O : 0, B, TT, C,
                  reverse ? 1 : 0, save ? 1 : 0, fp8 ? 1 : 0, is_bf16(xg),
                  images.data_ptr(), cur_stream()),
-      "gru forward");
+      "dr_gru_fwd");
   if (!heads) return {h_all, saves};
   return {h_all, saves, out};
 }
@@ -596,13 +554,13 @@ std::vector<at::Tensor> gru_seq_decode(at::Tensor xg, at::Tensor w_hh,
   auto h_last = at::empty({B, C, H}, xg.options());
   auto w_gemm = gru_w_gemm(w_hh);
   auto images = gru_operand_images(gamma, C);
-  gru_launch_check(
+  launch_check(
       dr_gru_decode(xg.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                     w_gemm.data_ptr(), b_hh.data_ptr<float>(), h0.data_ptr(),
                     wh_fwd.data_ptr(), out.data_ptr(), h_last.data_ptr(), B, TT,
                     C, (int)O, reverse ? 1 : 0, fp8 ? 1 : 0, is_bf16(xg), lens,
                     images.data_ptr(), cur_stream()),
-      "gru decode");
+      "dr_gru_decode");
   return {out, h_last};
 }
 
@@ -615,54 +573,35 @@ static std::vector<at::Tensor> gru_backward_impl(
     at::Tensor b_hh, at::Tensor h0, at::Tensor h_all, at::Tensor saves,
     bool reverse) {
   const at::cuda::CUDAGuard guard(grad_h.device());
-  TORCH_CHECK(grad_h.dim() == 4 && h_all.dim() == 4, "grad and h_all must be 4-D");
+  check_dtype(grad_h, "gru grad");
+  TORCH_CHECK(grad_h.is_cuda() && grad_h.dim() == 4 && h_all.dim() == 4,
+              "gru grad and h_all must be 4-D GPU tensors");
+  const auto dt = grad_h.scalar_type();
   int B = (int)h_all.size(0), TT = (int)h_all.size(1);
   int C = (int)h_all.size(2), H = (int)h_all.size(3);
-  TORCH_CHECK(H == 128);
-  TORCH_CHECK(grad_h.size(0) == B && grad_h.size(1) == TT && grad_h.size(2) == C,
-              "gru backward: grad leading dims must match h_all (B, T, C)");
+  TORCH_CHECK(H == 128, "fused GRU kernel requires hidden size 128, got ", H);
   int O = 0;
   if (wh_img != nullptr) {
     O = (int)grad_h.size(3);
     TORCH_CHECK(O >= 1 && O <= 32, "fused head gradient needs 1 <= O <= 32, got ", O);
-    TORCH_CHECK(wh_img->scalar_type() == at::kBFloat16 &&
-                    wh_img->sizes() == at::IntArrayRef({H, 32}) &&
-                    wh_img->is_contiguous() && wh_img->is_cuda(),
-                "wh_img must be the (H, 32) bf16 head weight image");
-  } else {
-    TORCH_CHECK(grad_h.size(3) == H, "grad_h must be (B, T, C, H)");
+    check_operand(*wh_img, "wh_img", grad_h, at::kBFloat16, {H, 32});
   }
-  TORCH_CHECK(xg.sizes() == at::IntArrayRef({B, TT, 3 * H}) &&
-                  h0.sizes() == at::IntArrayRef({B, C, H}) &&
-                  gamma.sizes() == at::IntArrayRef({C, 3 * H}) &&
-                  beta.sizes() == at::IntArrayRef({C, 3 * H}) &&
-                  b_hh.numel() == 3 * H,
-              "gru backward: operand shapes do not match h_all");
-  TORCH_CHECK(xg.is_contiguous() && h0.is_contiguous() && gamma.is_contiguous() &&
-              beta.is_contiguous());
-  TORCH_CHECK(h_all.scalar_type() == grad_h.scalar_type() &&
-              saves.scalar_type() == grad_h.scalar_type() &&
-              h0.scalar_type() == grad_h.scalar_type());
-  TORCH_CHECK(saves.numel() == (int64_t)B * TT * C * 2 * H,
-              "gru backward: saves tensor missing or wrong size (forward must "
-              "run with save=true)");
-  TORCH_CHECK(w_img.scalar_type() == at::kBFloat16 &&
-                  w_img.sizes() == at::IntArrayRef({H, 3 * H}) &&
-                  w_img.is_contiguous(),
-              "w_img must be the (H, 3H) bf16 pi-permuted W image");
-  TORCH_CHECK(w_fwd.scalar_type() == at::kBFloat16 &&
-                  w_fwd.sizes() == at::IntArrayRef({3 * H, H}) &&
-                  w_fwd.is_contiguous(),
-              "w_fwd must be the (3H, H) bf16 weight image");
-  TORCH_CHECK(b_hh.scalar_type() == at::kFloat && b_hh.is_contiguous());
-  auto dt = grad_h.scalar_type();
-  TORCH_CHECK(xg.scalar_type() == dt && gamma.scalar_type() == dt &&
-              beta.scalar_type() == dt);
-  TORCH_CHECK(grad_h.is_contiguous() && h_all.is_contiguous() && saves.is_contiguous());
+  check_operand(grad_h, "gru grad", grad_h, dt, {B, TT, C, wh_img ? O : H});
+  check_operand(h_all, "gru h_all", grad_h, dt, {B, TT, C, H});
+  // (B, T, C, 2H); empty when the forward ran without save
+  check_operand(saves, "gru saves", grad_h, dt, (int64_t)B * TT * C * 2 * H);
+  check_operand(xg, "x_gates", grad_h, dt, {B, TT, 3 * H});
+  check_operand(h0, "h0", grad_h, dt, {B, C, H});
+  check_operand(gamma, "gamma", grad_h, dt, {C, 3 * H});
+  check_operand(beta, "beta", grad_h, dt, {C, 3 * H});
+  check_operand(b_hh, "b_hh", grad_h, at::kFloat, 3 * H);
+  // the (H, 3H) pi-permuted and the (3H, H) natural bf16 images of W_hh
+  check_operand(w_img, "w_img", grad_h, at::kBFloat16, {H, 3 * H});
+  check_operand(w_fwd, "w_fwd", grad_h, at::kBFloat16, {3 * H, H});
   auto dpre = at::empty({B, TT, C, 4 * H}, grad_h.options());
   auto dh0 = at::empty({B, C, H}, grad_h.options().dtype(at::kFloat));
   auto images = gru_operand_images(gamma, C);
-  gru_launch_check(
+  launch_check(
       dr_gru_bwd(grad_h.data_ptr(), wh_img ? wh_img->data_ptr() : nullptr, O,
                  w_img.data_ptr(), w_fwd.data_ptr(), xg.data_ptr(),
                  gamma.data_ptr(), beta.data_ptr(), b_hh.data_ptr<float>(),
@@ -670,7 +609,7 @@ static std::vector<at::Tensor> gru_backward_impl(
                  dpre.data_ptr(), dh0.data_ptr<float>(), B, TT, C,
                  reverse ? 1 : 0, dt == at::kBFloat16, images.data_ptr(),
                  cur_stream()),
-      "gru backward");
+      "dr_gru_bwd");
   return {dpre, dh0};
 }
 
@@ -703,17 +642,15 @@ std::vector<at::Tensor> gru_bwd_reduce(at::Tensor dpre, at::Tensor gamma,
                                        at::Tensor xg, const std::string& mode) {
   const at::cuda::CUDAGuard guard(dpre.device());
   check_dtype(dpre, "dpre");
-  TORCH_CHECK(dpre.dim() == 4 && dpre.size(3) == 512);
+  TORCH_CHECK(dpre.is_cuda() && dpre.is_contiguous() && dpre.dim() == 4 &&
+                  dpre.size(3) == 512,
+              "gru_bwd_reduce: dpre must be a contiguous (B, T, C, 4H) GPU tensor");
   int64_t BT = dpre.size(0) * dpre.size(1);
   int C = (int)dpre.size(2);
   TORCH_CHECK(BT > 0 && C > 0, "gru_bwd_reduce: empty dpre");
-  TORCH_CHECK(gamma.sizes() == at::IntArrayRef({C, 384}) &&
-                  xg.sizes() == at::IntArrayRef({dpre.size(0), dpre.size(1), 384}),
-              "gru_bwd_reduce: gamma must be (C, 3H) and xg (B, T, 3H)");
-  TORCH_CHECK(gamma.scalar_type() == dpre.scalar_type() &&
-                  xg.scalar_type() == dpre.scalar_type() && gamma.is_cuda() &&
-                  xg.is_cuda(),
-              "gru_bwd_reduce: gamma and xg must match dpre's dtype and device");
+  check_operand(gamma, "gru_bwd_reduce gamma", dpre, dpre.scalar_type(), {C, 384});
+  check_operand(xg, "gru_bwd_reduce xg", dpre, dpre.scalar_type(),
+                {dpre.size(0), dpre.size(1), 384});
   int mode_id = 0;
   if (mode == "split") mode_id = 1;
   else if (mode == "fused") mode_id = 2;
@@ -721,20 +658,19 @@ std::vector<at::Tensor> gru_bwd_reduce(at::Tensor dpre, at::Tensor gamma,
   TORCH_CHECK(mode_id != 2 || C <= dr_gru_reduce_fused_max_c(),
               "gru_bwd_reduce: the fused mode covers C <= ",
               dr_gru_reduce_fused_max_c(), ", got C = ", C);
-  TORCH_CHECK(xg.is_contiguous() && gamma.is_contiguous() && dpre.is_contiguous());
   auto dxg = at::empty({dpre.size(0), dpre.size(1), 384}, dpre.options());
   auto dgamma = at::zeros({C, 384}, dpre.options().dtype(at::kFloat));
   auto dbeta = at::zeros({C, 512}, dpre.options().dtype(at::kFloat));
   // pi-layout staging images (see pi_permute_rows_kernel)
   auto gamma_pi = at::empty_like(gamma);
   auto xg_pi = at::empty_like(xg);
-  gru_launch_check(
+  launch_check(
       dr_gru_bwd_reduce(dpre.data_ptr(), gamma.data_ptr(), xg.data_ptr(),
                         dxg.data_ptr(), dgamma.data_ptr<float>(),
                         dbeta.data_ptr<float>(), gamma_pi.data_ptr(),
                         xg_pi.data_ptr(), BT, C, mode_id, is_bf16(dpre),
                         cur_stream()),
-      "gru backward reductions");
+      "dr_gru_bwd_reduce");
   return {dxg, dgamma, dbeta};
 }
 
@@ -761,6 +697,21 @@ static void mha_check_head_dim(int64_t D) {
               "head dim must be 8..64, mult of 8, got ", D);
 }
 
+// q is a contiguous (B, H, T, D) GPU tensor; each of `like_q` matches it in
+// device, dtype and shape.
+static void mha_checks(
+    const at::Tensor& q,
+    std::initializer_list<std::pair<const at::Tensor*, const char*>> like_q) {
+  check_dtype(q, "q");
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.is_contiguous(),
+              "q must be a contiguous (B, H, T, D) GPU tensor");
+  mha_check_head_dim(q.size(3));
+  TORCH_CHECK(q.size(1) < (1LL << 31) && q.size(2) < (1LL << 31),
+              "mha: H and T must be < 2^31");
+  for (const auto& [t, name] : like_q)
+    check_operand(*t, name, q, q.scalar_type(), q.sizes());
+}
+
 // kv_lengths (optional, (B,) int32): keys >= kv_lengths[b] are absent and
 // rows of o / lse at or past it are zero (inference only; mha_backward does
 // not know about lengths).
@@ -768,24 +719,18 @@ std::vector<at::Tensor> mha_forward(at::Tensor q, at::Tensor k, at::Tensor v,
                                     double scale,
                                     c10::optional<at::Tensor> kv_lengths) {
   const at::cuda::CUDAGuard guard(q.device());
-  check_dtype(q, "q");
-  TORCH_CHECK(q.dim() == 4, "q must be (B, H, T, D)");
-  TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
+  mha_checks(q, {{&k, "mha k"}, {&v, "mha v"}});
   int64_t B = q.size(0), NH = q.size(1);
   int T_len = (int)q.size(2), D = (int)q.size(3);
-  mha_check_head_dim(D);
   const int* kv_len = lengths_ptr(kv_lengths, q, B, "mha kv_lengths");
-  if (kv_len != nullptr)
-    TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes() &&
-                    k.scalar_type() == q.scalar_type() &&
-                    v.scalar_type() == q.scalar_type(),
-                "mha with kv_lengths: q, k, v must share shape and dtype");
   auto o = at::empty_like(q);
   auto lse = at::empty({B, NH, T_len}, q.options().dtype(at::kFloat));
+  if (q.numel() == 0) return {o, lse};
   const MhaLayout l = mha_bhtd(NH, T_len, D);
-  dr_mha_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-             lse.data_ptr<float>(), B, (int)NH, T_len, D, (float)scale,
-             is_bf16(q), kv_len, l.s, l.s, cur_stream());
+  launch_check(dr_mha_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                          lse.data_ptr<float>(), B, (int)NH, T_len, D,
+                          (float)scale, is_bf16(q), kv_len, l.s, l.s, cur_stream()),
+               "dr_mha_fwd");
   return {o, lse};
 }
 
@@ -795,19 +740,22 @@ std::vector<at::Tensor> mha_backward(at::Tensor q, at::Tensor k, at::Tensor v,
                                      at::Tensor o, at::Tensor dout, at::Tensor lse,
                                      double scale) {
   const at::cuda::CUDAGuard guard(q.device());
+  mha_checks(q, {{&k, "mha k"}, {&v, "mha v"}, {&o, "mha o"}, {&dout, "mha dout"}});
   int64_t B = q.size(0), NH = q.size(1);
   int T_len = (int)q.size(2), D = (int)q.size(3);
-  TORCH_CHECK(dout.is_contiguous() && o.is_contiguous());
+  check_operand(lse, "mha lse", q, at::kFloat, {B, NH, T_len});
   const bool writes_dq = dr_mha_bwd_writes_dq(T_len, D) != 0;
   auto dq = writes_dq ? at::empty_like(q)
                       : at::zeros(q.sizes(), q.options().dtype(at::kFloat));
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
+  if (q.numel() == 0) return {dq, dk, dv};
   const MhaLayout l = mha_bhtd(NH, T_len, D);
-  dr_mha_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-             dout.data_ptr(), lse.data_ptr<float>(), dq.data_ptr(),
-             dk.data_ptr(), dv.data_ptr(), B, (int)NH, T_len, D, (float)scale,
-             is_bf16(q), l.s, l.s, l.s, cur_stream());
+  launch_check(dr_mha_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                          dout.data_ptr(), lse.data_ptr<float>(), dq.data_ptr(),
+                          dk.data_ptr(), dv.data_ptr(), B, (int)NH, T_len, D,
+                          (float)scale, is_bf16(q), l.s, l.s, l.s, cur_stream()),
+               "dr_mha_bwd");
   return {dq, dk, dv};
 }
 
@@ -859,9 +807,11 @@ std::vector<at::Tensor> mha_packed_forward(at::Tensor qkv, int64_t n_heads,
   const char* base = static_cast<const char*>(qkv.data_ptr());
   const MhaLayout ql = mha_packed_part(s.NH, s.T, s.D);
   const MhaLayout ol = mha_bthd(s.NH, s.T, s.D);
-  dr_mha_fwd(base, base + part, base + 2 * part, o.data_ptr(),
-             lse.data_ptr<float>(), s.B, (int)s.NH, (int)s.T, (int)s.D,
-             (float)scale, is_bf16(qkv), nullptr, ql.s, ol.s, cur_stream());
+  launch_check(dr_mha_fwd(base, base + part, base + 2 * part, o.data_ptr(),
+                          lse.data_ptr<float>(), s.B, (int)s.NH, (int)s.T,
+                          (int)s.D, (float)scale, is_bf16(qkv), nullptr, ql.s,
+                          ol.s, cur_stream()),
+               "dr_mha_fwd");
   return {o, lse};
 }
 
@@ -894,11 +844,14 @@ at::Tensor mha_packed_backward(at::Tensor qkv, int64_t n_heads, at::Tensor o,
   at::Tensor dq32;
   if (!writes_dq)
     dq32 = at::zeros({s.B, s.T, s.NH, s.D}, qkv.options().dtype(at::kFloat));
-  dr_mha_bwd(base, base + part, base + 2 * part, o.data_ptr(), dout.data_ptr(),
-             lse.data_ptr<float>(), writes_dq ? (void*)dbase : dq32.data_ptr(),
-             dbase + part, dbase + 2 * part, s.B, (int)s.NH, (int)s.T, (int)s.D,
-             (float)scale, is_bf16(qkv), ql.s, ol.s, writes_dq ? ql.s : ol.s,
-             cur_stream());
+  launch_check(
+      dr_mha_bwd(base, base + part, base + 2 * part, o.data_ptr(),
+                 dout.data_ptr(), lse.data_ptr<float>(),
+                 writes_dq ? (void*)dbase : dq32.data_ptr(), dbase + part,
+                 dbase + 2 * part, s.B, (int)s.NH, (int)s.T, (int)s.D,
+                 (float)scale, is_bf16(qkv), ql.s, ol.s, writes_dq ? ql.s : ol.s,
+                 cur_stream()),
+      "dr_mha_bwd");
   if (!writes_dq) dqkv.select(2, 0).copy_(dq32);
   return dqkv;
 }
@@ -928,18 +881,14 @@ std::vector<at::Tensor> band_scores(at::Tensor out, at::Tensor measured,
   const int64_t N = out.size(0), T = out.size(1), M = out.size(2);
   TORCH_CHECK(T < (1LL << 31) && M < (1LL << 31) && N * M < (1LL << 31) * 64,
               "band_scores shape too large");
-  auto f32_on_dev = [&](const at::Tensor& t, at::IntArrayRef shape,
-                        const char* name) {
-    TORCH_CHECK(t.scalar_type() == at::kFloat && t.device() == out.device() &&
-                    t.is_contiguous() && t.sizes() == shape,
-                "band_scores ", name, " must be a contiguous f32 tensor of shape ",
-                shape, " on out's device");
-  };
-  f32_on_dev(measured, {N, T, M}, "measured");
-  f32_on_dev(y_min, {M}, "y_min");
-  f32_on_dev(y_scale, {M}, "y_scale");
-  if (base.has_value()) f32_on_dev(*base, {N, T, M}, "base");
-  if (conformal.has_value()) f32_on_dev(*conformal, {M}, "conformal");
+  const int64_t ntm[] = {N, T, M}, m1[] = {M};
+  check_operand(measured, "band_scores measured", out, at::kFloat, ntm);
+  check_operand(y_min, "band_scores y_min", out, at::kFloat, m1);
+  check_operand(y_scale, "band_scores y_scale", out, at::kFloat, m1);
+  if (base.has_value())
+    check_operand(*base, "band_scores base", out, at::kFloat, ntm);
+  if (conformal.has_value())
+    check_operand(*conformal, "band_scores conformal", out, at::kFloat, m1);
   if (lengths.has_value())
     TORCH_CHECK(lengths->dim() == 1, "band_scores lengths must be (N,)");
   const int* lens = lengths_ptr(lengths, out, N, "band_scores lengths");
@@ -961,7 +910,7 @@ std::vector<at::Tensor> band_scores(at::Tensor out, at::Tensor measured,
     n_observed.zero_();
     return {scores, flags, max_score, n_flagged, first_flag, n_observed, bands};
   }
-  gru_launch_check(
+  launch_check(
       dr_sanity_scores(out.data_ptr(), measured.data_ptr<float>(),
                        base.has_value() ? base->data_ptr<float>() : nullptr,
                        y_min.data_ptr<float>(), y_scale.data_ptr<float>(),
@@ -974,7 +923,7 @@ std::vector<at::Tensor> band_scores(at::Tensor out, at::Tensor measured,
                        n_observed.data_ptr<int>(),
                        want_bands ? bands.data_ptr<float>() : nullptr,
                        is_bf16(out), cur_stream()),
-      "band_scores");
+      "dr_sanity_scores");
   return {scores, flags, max_score, n_flagged, first_flag, n_observed, bands};
 }
 

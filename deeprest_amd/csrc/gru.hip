@@ -30,8 +30,8 @@
 //
 // Fixed geometry: H = 128, 3H = 384, 64 rows/block, 4 waves, 256 threads.
 #include "common.h"
-
-#include <type_traits>
+#include "kernels.h"
+#include "launch.h"
 
 namespace dr {
 
@@ -1550,15 +1550,7 @@ __global__ __launch_bounds__(RF_WAVES * DR_WAVE) void gru_reduce_fused_kernel(
 }
 
 // ------------------------------------------------------------- launchers
-// Every launch function returns the hipError_t of its set-up or launch, and
-// the dr_gru_* entries hand it to the binding as an int (0 = success).
-
-// run f with the IO element type as a tag: f(TypeTag<uint16_t>) or <float>
-template <typename T> struct TypeTag { using type = T; };
-template <typename F>
-static hipError_t with_io_type(int is_bf16, F&& f) {
-  return is_bf16 ? f(TypeTag<uint16_t>{}) : f(TypeTag<float>{});
-}
+// TypeTag / with_io_type / allow_lds and the status convention: launch.h.
 
 // The forward kernel's tile variant, chosen once for the sequence and the
 // decode entry: f(FwdTile<FP8, NSUB>).
@@ -1582,17 +1574,6 @@ static hipError_t with_fwd_tile(int B, int C, int fp8, F&& f) {
 // the sequence entry and dr_gru_fwd_fuses_heads both ask here.
 template <typename Tile>
 static constexpr bool fwd_train_heads(Tile) { return !Tile::FP8 && Tile::NSUB == 2; }
-
-// Raises a kernel's dynamic-LDS limit.  Each launch function keeps the result
-// in a function-local static: set once per instantiation (thread-safe, and
-// only for the variant that runs), a failure is returned by every later call.
-// Once per process, not per device: a second device used by the same process
-// would launch without the attribute.
-template <typename K>
-static hipError_t allow_lds(K kernel, int bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
 
 // Fills the operand-image buffer (see OperandImages) on the stream.
 template <typename T>
@@ -1768,18 +1749,13 @@ static hipError_t gru_reduce_launch(const void* dpre, const void* gamma,
 
 extern "C" {
 
-// Bytes of the operand-image buffer that dr_gru_fwd, dr_gru_decode and
-// dr_gru_bwd take as `images`: device memory, 16-byte aligned, contents
-// undefined on entry.  The entries fill and read it on the stream where the
-// variant they pick streams its FiLM operands.
+// Entry contracts: kernels.h.
+
 int64_t dr_gru_operand_images_bytes(int C, int is_bf16) {
   return is_bf16 ? dr::OperandImages<uint16_t>::total(C)
                  : dr::OperandImages<float>::total(C);
 }
 
-// 1 when a saving forward at (B, C) runs the quantile-head projection inside
-// the kernel (dr_gru_fwd then takes wh_fwd / out / O), 0 when the caller does
-// the projection itself.
 int dr_gru_fwd_fuses_heads(int B, int C) {
   bool fuses = false;
   (void)dr::with_fwd_tile(B, C, 0, [&](auto tile) {
@@ -1789,9 +1765,6 @@ int dr_gru_fwd_fuses_heads(int B, int C) {
   return fuses ? 1 : 0;
 }
 
-// wh_fwd != nullptr (save only, where dr_gru_fwd_fuses_heads says so): the
-// (32, H) bf16 head weight image of dr_gru_decode; the kernel also writes
-// out (B, TT, C, O).
 int dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
                const void* w_hh, const float* b_hh, const void* h0, void* h_all,
                void* saves, const void* wh_fwd, void* out, int O, int B, int TT,
@@ -1819,10 +1792,6 @@ int dr_gru_fwd(const void* xg, const void* gamma, const void* beta,
   });
 }
 
-// Inference decode: GRU sequence + head projection, no h_all.  wh_fwd is the
-// (32, H) bf16 head weight image, rows >= O exact zero.  lens == nullptr:
-// every row runs all TT steps; otherwise (B,) int32 per-sample lengths on the
-// device and out must arrive zeroed.
 int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
                   const void* w_hh, const float* b_hh, const void* h0,
                   const void* wh_fwd, void* out, void* h_last, int B, int TT,
@@ -1843,9 +1812,6 @@ int dr_gru_decode(const void* xg, const void* gamma, const void* beta,
   return (int)(lens != nullptr ? run(std::true_type{}) : run(std::false_type{}));
 }
 
-// wh_img == nullptr: grad is grad_h (B, TT, C, H), the unfused path.
-// Otherwise grad is the heads' grad_part (B, TT, C, O) and wh_img the (H, 32)
-// bf16 zero-padded transposed head weight image.
 int dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
                const void* w_fwd, const void* xg, const void* gamma,
                const void* beta, const float* b_hh, const void* h0,
@@ -1870,12 +1836,8 @@ int dr_gru_bwd(const void* grad, const void* wh_img, int O, const void* w_img,
   return (int)(fused ? run(std::true_type{}) : run(std::false_type{}));
 }
 
-// largest C the single-pass reduce kernel covers
 int dr_gru_reduce_fused_max_c() { return dr::REDUCE_FUSED_MAX_C; }
 
-// mode: 0 auto (single pass up to its C limit, the two-kernel form above it),
-// 1 the two-kernel form, 2 the single pass (an error above its limit).
-// returns the first failing launch's error
 int dr_gru_bwd_reduce(const void* dpre, const void* gamma, const void* xg,
                       void* dxg, float* dgamma, float* dbeta, void* gamma_pi,
                       void* xg_pi, int64_t BT, int C, int mode, int is_bf16,

@@ -10,6 +10,8 @@
 // of paying a ~280 MB f32 cast of the output tensor each step (the gradient
 // is sign(e)-based quantile constants, so bf16 inputs lose nothing).
 #include "common.h"
+#include "kernels.h"
+#include "launch.h"
 
 namespace dr {
 
@@ -249,83 +251,74 @@ static MaskedGeom masked_geom(int64_t R, int M, int rows_per_thread) {
   return g;
 }
 
+// the unmasked kernels: grid-stride over N, at least one block
+static dim3 pinball_grid(int64_t N) {
+  return dim3((unsigned)std::max<int64_t>(std::min<int64_t>((N + 255) / 256, 2048), 1));
+}
+
 }  // namespace dr
 
+// Entry contracts: kernels.h.
 extern "C" {
 
-// Copies of the (M,) workspaces that the forward spreads its flushes over: 16
-// while one column tile holds every metric (M <= 256: all ~2048 blocks would
-// add into the same M addresses), 1 above (the tiles already spread them and
-// the finalize block would have 16x to read).
 int dr_pinball_masked_slots(int M) { return M <= DR_PB_THREADS ? 16 : 1; }
 
-// wsum / wcnt: (slots, M) each, zeroed by the caller.  R > 0 and M > 0.
-void dr_pinball_masked_fwd(const void* out, const float* labels,
-                           const float* quantiles, int Q, int64_t R, int M,
-                           float* wsum, int* wcnt, float* loss, float* w,
-                           int is_bf16, hipStream_t stream) {
+int dr_pinball_masked_fwd(const void* out, const float* labels,
+                          const float* quantiles, int Q, int64_t R, int M,
+                          float* wsum, int* wcnt, float* loss, float* w,
+                          int is_bf16, hipStream_t stream) {
   const dr::MaskedGeom g = dr::masked_geom(R, M, 4);
   const int S = dr_pinball_masked_slots(M);
-  if (is_bf16)
-    hipLaunchKernelGGL((dr::pinball_masked_fwd_kernel<uint16_t, 8>), g.grid,
-                       dim3(g.block), 0, stream, (const uint16_t*)out, labels,
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    using T = typename decltype(io)::type;
+    hipLaunchKernelGGL((dr::pinball_masked_fwd_kernel<T, 8>), g.grid,
+                       dim3(g.block), 0, stream, (const T*)out, labels,
                        quantiles, Q, R, M, g.cw, g.rw, S, wsum, wcnt);
-  else
-    hipLaunchKernelGGL((dr::pinball_masked_fwd_kernel<float, 8>), g.grid,
-                       dim3(g.block), 0, stream, (const float*)out, labels,
-                       quantiles, Q, R, M, g.cw, g.rw, S, wsum, wcnt);
-  hipLaunchKernelGGL(dr::pinball_masked_finalize_kernel, dim3(1),
-                     dim3(DR_PB_THREADS), 0, stream, wsum, wcnt, M, S, loss,
-                     w);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(dr::pinball_masked_finalize_kernel, dim3(1),
+                       dim3(DR_PB_THREADS), 0, stream, wsum, wcnt, M, S, loss,
+                       w);
+    return hipGetLastError();
+  });
 }
 
-void dr_pinball_masked_bwd(const void* out, const float* labels,
-                           const float* quantiles, int Q, int64_t R, int M,
-                           const float* grad_loss, const float* w, void* dout,
-                           int is_bf16, hipStream_t stream) {
+int dr_pinball_masked_bwd(const void* out, const float* labels,
+                          const float* quantiles, int Q, int64_t R, int M,
+                          const float* grad_loss, const float* w, void* dout,
+                          int is_bf16, hipStream_t stream) {
   const dr::MaskedGeom g = dr::masked_geom(R, M, 1);
-  if (is_bf16)
-    hipLaunchKernelGGL((dr::pinball_masked_bwd_kernel<uint16_t, 8>), g.grid,
-                       dim3(g.block), 0, stream, (const uint16_t*)out, labels,
-                       quantiles, Q, R, M, g.cw, g.rw, grad_loss, w,
-                       (uint16_t*)dout);
-  else
-    hipLaunchKernelGGL((dr::pinball_masked_bwd_kernel<float, 8>), g.grid,
-                       dim3(g.block), 0, stream, (const float*)out, labels,
-                       quantiles, Q, R, M, g.cw, g.rw, grad_loss, w,
-                       (float*)dout);
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    using T = typename decltype(io)::type;
+    hipLaunchKernelGGL((dr::pinball_masked_bwd_kernel<T, 8>), g.grid,
+                       dim3(g.block), 0, stream, (const T*)out, labels,
+                       quantiles, Q, R, M, g.cw, g.rw, grad_loss, w, (T*)dout);
+    return hipGetLastError();
+  });
 }
 
-void dr_pinball_fwd(const void* out, const float* labels, const float* quantiles,
-                    int Q, int64_t N, float inv_count, float* loss, int is_bf16,
-                    hipStream_t stream) {
-  const int block = 256;
-  int grid = (int)std::min<int64_t>((N + block - 1) / block, 2048);
-  if (grid == 0) grid = 1;
-  if (is_bf16)
-    hipLaunchKernelGGL((dr::pinball_fwd_kernel<uint16_t, 8>), dim3(grid),
-                       dim3(block), 0, stream, (const uint16_t*)out, labels,
-                       quantiles, Q, N, inv_count, loss);
-  else
-    hipLaunchKernelGGL((dr::pinball_fwd_kernel<float, 8>), dim3(grid),
-                       dim3(block), 0, stream, (const float*)out, labels,
-                       quantiles, Q, N, inv_count, loss);
+int dr_pinball_fwd(const void* out, const float* labels, const float* quantiles,
+                   int Q, int64_t N, float inv_count, float* loss, int is_bf16,
+                   hipStream_t stream) {
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    using T = typename decltype(io)::type;
+    hipLaunchKernelGGL((dr::pinball_fwd_kernel<T, 8>), dr::pinball_grid(N),
+                       dim3(256), 0, stream, (const T*)out, labels, quantiles, Q,
+                       N, inv_count, loss);
+    return hipGetLastError();
+  });
 }
 
-void dr_pinball_bwd(const void* out, const float* labels, const float* quantiles,
-                    int Q, int64_t N, const float* grad_loss, float inv_n,
-                    void* dout, int is_bf16, hipStream_t stream) {
-  const int block = 256;
-  int grid = (int)std::min<int64_t>((N + block - 1) / block, 2048);
-  if (grid == 0) grid = 1;
-  if (is_bf16)
-    hipLaunchKernelGGL((dr::pinball_bwd_kernel<uint16_t, 8>), dim3(grid),
-                       dim3(block), 0, stream, (const uint16_t*)out, labels,
-                       quantiles, Q, N, grad_loss, inv_n, (uint16_t*)dout);
-  else
-    hipLaunchKernelGGL((dr::pinball_bwd_kernel<float, 8>), dim3(grid),
-                       dim3(block), 0, stream, (const float*)out, labels,
-                       quantiles, Q, N, grad_loss, inv_n, (float*)dout);
+int dr_pinball_bwd(const void* out, const float* labels, const float* quantiles,
+                   int Q, int64_t N, const float* grad_loss, float inv_n,
+                   void* dout, int is_bf16, hipStream_t stream) {
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    using T = typename decltype(io)::type;
+    hipLaunchKernelGGL((dr::pinball_bwd_kernel<T, 8>), dr::pinball_grid(N),
+                       dim3(256), 0, stream, (const T*)out, labels, quantiles, Q,
+                       N, grad_loss, inv_n, (T*)dout);
+    return hipGetLastError();
+  });
 }
 
 }  // extern "C"
+

@@ -17,6 +17,8 @@
 // HAS_MASK off: p == 0 or eval, no RNG work and no seed tensor.
 // HAS_NORM off: plain dropout_add (no stats, no w/b).
 #include "common.h"
+#include "kernels.h"
+#include "launch.h"
 
 namespace dr {
 
@@ -498,112 +500,104 @@ dal_bwd_stream(const T* __restrict__ d_normed, const T* __restrict__ d_r_out,
 }
 
 // ---------------------------------------------------------------- launchers
+// D picks the kernel: vec4, 4 or 16 values per lane, or the streaming body.
 template <typename T, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
-static void dal_fwd_launch_t(const void* branch, const void* residual, const float* w,
-                             const float* b, const int64_t* seed, uint32_t thr,
-                             float scale, void* r_out, void* normed, float* mean,
-                             float* rstd, int64_t n_rows, int D, float eps,
-                             hipStream_t stream) {
+static hipError_t dal_fwd_launch(const void* branch, const void* residual,
+                                 const float* w, const float* b,
+                                 const int64_t* seed, uint32_t thr, float scale,
+                                 void* r_out, void* normed, float* mean,
+                                 float* rstd, int64_t n_rows, int D, float eps,
+                                 hipStream_t stream) {
   const int block = 256;
   const int waves = block / DR_WAVE;
   int grid = (int)std::min<int64_t>((n_rows + waves - 1) / waves, 2048);
   if (grid == 0) grid = 1;
-#define DR_DAL_FWD(...)                                                        \
-  hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(block), 0, stream,             \
-                     (const T*)branch, (const T*)residual, w, b, seed, thr,    \
-                     scale, (T*)r_out, (T*)normed, mean, rstd, n_rows, D, eps)
-  if ((D % 4) == 0 && D <= 4 * DR_WAVE) {
-    DR_DAL_FWD(dal_fwd_vec4<T, HAS_ADD, HAS_MASK, HAS_NORM>);
-  } else if (D <= 256) {
-    DR_DAL_FWD(dal_fwd_kernel<T, 4, HAS_ADD, HAS_MASK, HAS_NORM>);
-  } else if (D <= 1024) {
-    DR_DAL_FWD(dal_fwd_kernel<T, 16, HAS_ADD, HAS_MASK, HAS_NORM>);
-  } else {
-    DR_DAL_FWD(dal_fwd_stream<T, HAS_ADD, HAS_MASK, HAS_NORM>);
-  }
-#undef DR_DAL_FWD
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream,
+                       (const T*)branch, (const T*)residual, w, b, seed, thr,
+                       scale, (T*)r_out, (T*)normed, mean, rstd, n_rows, D, eps);
+    return hipGetLastError();
+  };
+  if ((D % 4) == 0 && D <= 4 * DR_WAVE)
+    return launch(dal_fwd_vec4<T, HAS_ADD, HAS_MASK, HAS_NORM>);
+  if (D <= 256) return launch(dal_fwd_kernel<T, 4, HAS_ADD, HAS_MASK, HAS_NORM>);
+  if (D <= 1024) return launch(dal_fwd_kernel<T, 16, HAS_ADD, HAS_MASK, HAS_NORM>);
+  return launch(dal_fwd_stream<T, HAS_ADD, HAS_MASK, HAS_NORM>);
 }
 
 template <typename T, bool HAS_ADD, bool HAS_MASK, bool HAS_NORM>
-static void dal_bwd_launch_t(const void* d_normed, const void* d_r_out,
-                             const void* r_out, const float* w, const float* mean,
-                             const float* rstd, const int64_t* seed, uint32_t thr,
-                             float scale, void* d_res, void* d_branch,
-                             float* dwdb_part, int n_blocks, int64_t n_rows, int D,
-                             hipStream_t stream) {
+static hipError_t dal_bwd_launch(const void* d_normed, const void* d_r_out,
+                                 const void* r_out, const float* w,
+                                 const float* mean, const float* rstd,
+                                 const int64_t* seed, uint32_t thr, float scale,
+                                 void* d_res, void* d_branch, float* dwdb_part,
+                                 int n_blocks, int64_t n_rows, int D,
+                                 hipStream_t stream) {
   const int block = 256;
   const size_t smem = HAS_NORM ? 2 * D * sizeof(float) : 0;
-#define DR_DAL_BWD(...)                                                        \
-  hipLaunchKernelGGL((__VA_ARGS__), dim3(n_blocks), dim3(block), smem, stream,      \
-                     (const T*)d_normed, (const T*)d_r_out, (const T*)r_out, w, \
-                     mean, rstd, seed, thr, scale, (T*)d_res, (T*)d_branch,    \
-                     dwdb_part, n_rows, D)
-  if ((D % 4) == 0 && D <= 4 * DR_WAVE) {
-    DR_DAL_BWD(dal_bwd_vec4<T, HAS_ADD, HAS_MASK, HAS_NORM>);
-  } else if (D <= 256) {
-    DR_DAL_BWD(dal_bwd_kernel<T, 4, HAS_ADD, HAS_MASK, HAS_NORM>);
-  } else if (D <= 1024) {
-    DR_DAL_BWD(dal_bwd_kernel<T, 16, HAS_ADD, HAS_MASK, HAS_NORM>);
-  } else {
-    DR_DAL_BWD(dal_bwd_stream<T, HAS_ADD, HAS_MASK, HAS_NORM>);
-  }
-#undef DR_DAL_BWD
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(block), smem, stream,
+                       (const T*)d_normed, (const T*)d_r_out, (const T*)r_out, w,
+                       mean, rstd, seed, thr, scale, (T*)d_res, (T*)d_branch,
+                       dwdb_part, n_rows, D);
+    return hipGetLastError();
+  };
+  if ((D % 4) == 0 && D <= 4 * DR_WAVE)
+    return launch(dal_bwd_vec4<T, HAS_ADD, HAS_MASK, HAS_NORM>);
+  if (D <= 256) return launch(dal_bwd_kernel<T, 4, HAS_ADD, HAS_MASK, HAS_NORM>);
+  if (D <= 1024) return launch(dal_bwd_kernel<T, 16, HAS_ADD, HAS_MASK, HAS_NORM>);
+  return launch(dal_bwd_stream<T, HAS_ADD, HAS_MASK, HAS_NORM>);
 }
+
+constexpr std::true_type on{};
+constexpr std::false_type off{};
 
 }  // namespace dr
 
-// ---- C ABI launchers (called from bindings.cpp) ----
-// has_mask: seed != nullptr; has_norm: w != nullptr.  branch == nullptr
-// (forward) / d_r_out == nullptr (backward) is plain LayerNorm, which takes
-// no seed and needs w: bindings.cpp checks both before it calls.
+// Entry contracts: kernels.h.  The ladders below name every (HAS_ADD,
+// HAS_MASK, HAS_NORM) instance that exists.
 extern "C" {
 
-void dr_dropout_add_ln_fwd(const void* branch, const void* residual, const float* w,
-                           const float* b, const int64_t* seed, uint32_t thr,
-                           float scale, void* r_out, void* normed, float* mean,
-                           float* rstd, int64_t n_rows, int D, float eps,
-                           int is_bf16, hipStream_t stream) {
+int dr_dropout_add_ln_fwd(const void* branch, const void* residual, const float* w,
+                          const float* b, const int64_t* seed, uint32_t thr,
+                          float scale, void* r_out, void* normed, float* mean,
+                          float* rstd, int64_t n_rows, int D, float eps,
+                          int is_bf16, hipStream_t stream) {
   const bool a = branch != nullptr, m = seed != nullptr, n = w != nullptr;
-#define DR_DAL_GO(T, A, M, N)                                                  \
-  dr::dal_fwd_launch_t<T, A, M, N>(branch, residual, w, b, seed, thr, scale,   \
-                                   r_out, normed, mean, rstd, n_rows, D, eps,  \
-                                   stream)
-#define DR_DAL_T(T)                                                            \
-  do {                                                                         \
-    if (!a) DR_DAL_GO(T, false, false, true);                                  \
-    else if (m && n) DR_DAL_GO(T, true, true, true);                           \
-    else if (m) DR_DAL_GO(T, true, true, false);                               \
-    else if (n) DR_DAL_GO(T, true, false, true);                               \
-    else DR_DAL_GO(T, true, false, false);                                     \
-  } while (0)
-  if (is_bf16) DR_DAL_T(uint16_t); else DR_DAL_T(float);
-#undef DR_DAL_T
-#undef DR_DAL_GO
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    auto go = [&](auto A, auto M, auto N) {
+      return dr::dal_fwd_launch<typename decltype(io)::type, decltype(A)::value,
+                                decltype(M)::value, decltype(N)::value>(
+          branch, residual, w, b, seed, thr, scale, r_out, normed, mean, rstd,
+          n_rows, D, eps, stream);
+    };
+    using dr::on, dr::off;
+    if (!a) return go(off, off, on);
+    if (m) return n ? go(on, on, on) : go(on, on, off);
+    return n ? go(on, off, on) : go(on, off, off);
+  });
 }
 
-// at least one of seed / w is non-null: without either, d_branch and
-// d_residual are both d_r_out and there is nothing to launch
-void dr_dropout_add_ln_bwd(const void* d_normed, const void* d_r_out,
-                           const void* r_out, const float* w, const float* mean,
-                           const float* rstd, const int64_t* seed, uint32_t thr,
-                           float scale, void* d_res, void* d_branch,
-                           float* dwdb_part, int n_blocks, int64_t n_rows, int D,
-                           int is_bf16, hipStream_t stream) {
+int dr_dropout_add_ln_bwd(const void* d_normed, const void* d_r_out,
+                          const void* r_out, const float* w, const float* mean,
+                          const float* rstd, const int64_t* seed, uint32_t thr,
+                          float scale, void* d_res, void* d_branch,
+                          float* dwdb_part, int n_blocks, int64_t n_rows, int D,
+                          int is_bf16, hipStream_t stream) {
   const bool a = d_r_out != nullptr, m = seed != nullptr, n = w != nullptr;
-#define DR_DAL_GO(T, A, M, N)                                                  \
-  dr::dal_bwd_launch_t<T, A, M, N>(d_normed, d_r_out, r_out, w, mean, rstd,    \
-                                   seed, thr, scale, d_res, d_branch,          \
-                                   dwdb_part, n_blocks, n_rows, D, stream)
-#define DR_DAL_T(T)                                                            \
-  do {                                                                         \
-    if (!a) DR_DAL_GO(T, false, false, true);                                  \
-    else if (m && n) DR_DAL_GO(T, true, true, true);                           \
-    else if (m) DR_DAL_GO(T, true, true, false);                               \
-    else if (n) DR_DAL_GO(T, true, false, true);                               \
-  } while (0)
-  if (is_bf16) DR_DAL_T(uint16_t); else DR_DAL_T(float);
-#undef DR_DAL_T
-#undef DR_DAL_GO
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    auto go = [&](auto A, auto M, auto N) {
+      return dr::dal_bwd_launch<typename decltype(io)::type, decltype(A)::value,
+                                decltype(M)::value, decltype(N)::value>(
+          d_normed, d_r_out, r_out, w, mean, rstd, seed, thr, scale, d_res,
+          d_branch, dwdb_part, n_blocks, n_rows, D, stream);
+    };
+    using dr::on, dr::off;
+    if (!a) return go(off, off, on);
+    if (m) return n ? go(on, on, on) : go(on, on, off);
+    // no mask and no norm: nothing to launch (there is no such instance)
+    return n ? go(on, off, on) : hipSuccess;
+  });
 }
 
 }  // extern "C"

@@ -26,6 +26,8 @@
 // positions t >= L are never loaded (score NaN, flag 0, bands NaN, in no
 // summary; a run ends at L).  Nothing stored there can reach a valid output.
 #include "common.h"
+#include "kernels.h"
+#include "launch.h"
 
 namespace dr {
 
@@ -214,10 +216,9 @@ sanity_kernel(const T* __restrict__ out,            // (N, TT, M, 3)
 
 }  // namespace dr
 
+// Entry contract: kernels.h.
 extern "C" {
 
-// N * M > 0, TT > 0, min_run >= 1 (the binding checks).  Returns the HIP error
-// of the launch, 0 on success.
 int dr_sanity_scores(const void* out, const float* measured, const float* base,
                      const float* y_min, const float* y_scale,
                      const float* conformal, const int* lengths, int64_t N,
@@ -228,19 +229,15 @@ int dr_sanity_scores(const void* out, const float* measured, const float* base,
   const int64_t NM = N * M;
   const dim3 grid((unsigned)((NM + DR_SANITY_THREADS - 1) / DR_SANITY_THREADS));
   const dim3 block(DR_SANITY_THREADS);
-  if (is_bf16)
-    hipLaunchKernelGGL(dr::sanity_kernel<uint16_t>, grid, block, 0, stream,
-                       (const uint16_t*)out, measured, base, y_min, y_scale,
-                       conformal, lengths, NM, TT, M, log1p, threshold, min_run,
-                       scores, flags, max_score, n_flagged, first_flag,
-                       n_observed, bands);
-  else
-    hipLaunchKernelGGL(dr::sanity_kernel<float>, grid, block, 0, stream,
-                       (const float*)out, measured, base, y_min, y_scale,
-                       conformal, lengths, NM, TT, M, log1p, threshold, min_run,
-                       scores, flags, max_score, n_flagged, first_flag,
-                       n_observed, bands);
-  return (int)hipGetLastError();
+  return (int)dr::with_io_type(is_bf16, [&](auto io) {
+    using T = typename decltype(io)::type;
+    hipLaunchKernelGGL(dr::sanity_kernel<T>, grid, block, 0, stream,
+                       (const T*)out, measured, base, y_min, y_scale, conformal,
+                       lengths, NM, TT, M, log1p, threshold, min_run, scores,
+                       flags, max_score, n_flagged, first_flag, n_observed,
+                       bands);
+    return hipGetLastError();
+  });
 }
 
 }  // extern "C"

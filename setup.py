@@ -30,8 +30,10 @@ setup(
             name="deeprest_amd._C",
             sources=sources,
             extra_compile_args={
-                "cxx": ["-O3", "-std=c++17"],
-                "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],
+                # every launching entry returns a [[nodiscard]] status (kernels.h)
+                "cxx": ["-O3", "-std=c++17", "-Werror=unused-result"],
+                "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950",
+                         "-Werror=unused-result"],
             },
         )
     ],
