@@ -18,7 +18,7 @@ from .gru import (fused_gru_decode, fused_gru_heads, fused_gru_sequence,
 from .layernorm import layer_norm, reference_layer_norm
 from .residual_norm import (dropout_add, dropout_add_layer_norm, philox_keep_mask,
                             reference_dropout_add_layer_norm)
-from .attention import mha_forward, mha_packed, reference_mha
+from .attention import mha_forward, mha_packed, reference_mha, reference_mha_step
 from .pinball import (masked_pinball_loss, pinball_loss,
                       reference_masked_pinball_loss, reference_pinball_loss)
 from .adam import fused_adam_step, reference_adam_step
@@ -41,6 +41,7 @@ __all__ = [
     "mha_forward",
     "mha_packed",
     "reference_mha",
+    "reference_mha_step",
     "pinball_loss",
     "reference_pinball_loss",
     "masked_pinball_loss",

@@ -73,6 +73,121 @@ def reference_mha(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return torch.where(row, torch.matmul(p, v), zero)
 
 
+def _bf16_round(x: torch.Tensor) -> torch.Tensor:
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+def reference_mha_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                       dout: Optional[torch.Tensor],
+                       scale: Optional[float] = None,
+                       kv_lengths: Optional[torch.Tensor] = None, *,
+                       emulate: Optional[str] = None):
+    """Attention forward and backward written out, no autograd.
+
+    q, k, v, dout: ``(B, H, T, D)``.  Returns ``(o, lse, dq, dk, dv)``.
+
+    ``emulate=None`` is the reference, in the dtype of the inputs (the tests
+    pass float64)::
+
+        S = q k^T * scale;  lse = logsumexp(S);  P = exp(S - lse);  o = P v
+        Drow = rowsum(dout * o);  dS = P * (dout v^T - Drow) * scale
+        dq = dS k;  dk = dS^T q;  dv = P^T dout
+
+    With ``kv_lengths`` (B,) the semantics are those of :func:`reference_mha`:
+    lengths clamped to [1, T], padded keys absent, padded q/k/v replaced by
+    zero through a select, rows of ``o`` and ``lse`` at or past the length
+    exactly zero.  That mode is forward only: ``dout`` must be None and the
+    three gradients come back None.
+
+    ``emulate="bf16"`` or ``"f32"`` (the IO dtype of the kernels) is an
+    emulation of the arithmetic of ``csrc/attention.hip``: float32 throughout,
+    with a bf16 round trip where the four kernels round.  Its distance from the
+    float64 reference is the error the number formats commit on these inputs.
+    The roundings, each with the line of the flash-style bodies it mirrors (the
+    whole-head tile bodies round at the same places):
+
+    - q, k, v, dout as MFMA operands: ``f2bf(... ldf(qb ...))`` of the q
+      fragments, of the K / V^T staging (forward), of ``tk`` / ``tv`` and the
+      ``q_lds`` / ``do_lds`` staging (backward); tile bodies ``ld8`` /
+      ``pack8``.  For bf16 IO this changes nothing;
+    - ``S * scale`` in float32 after the product (``s_acc[nt][i] * scale``);
+    - the row sum ``l`` over the unrounded exponentials
+      (``l_run[i] += group16_sum(p[0][i] + p[1][i])``), P rounded before
+      ``P v`` (``f2bf(p[nt][i])`` into ``p_lds``; tile: ``acc_pair_frag``);
+    - ``o`` divided by ``l`` after the product (``o_acc[nt][i] * inv_l``);
+      ``lse = m + log(l)`` in float32;
+    - ``Drow`` in float32 from the IO-dtype values of dout and of the stored o
+      (``s += ldf(dob ...) * ldf(ob ...)``): dout is not operand-rounded here;
+    - the backward's ``P = exp(S * scale - lse)`` with the stored float32 lse
+      (``__expf(st[nt][i] * scale - l)``), rounded before ``P^T dout``
+      (``f2bf(p)`` into ``my_p``);
+    - ``dS = P * (dP - Drow) * scale`` from the unrounded P, rounded after the
+      multiplication by ``scale`` (``f2bf(st[nt][i])``) before its three
+      products;
+    - bf16 IO: o, dq, dk, dv rounded to bf16 on store (``stf``; the flash dq
+      is summed in float32 and cast once); f32 IO: nothing more.
+
+    Not modelled: the order of the float32 sums inside an MFMA and across the
+    flash-style key steps and dq atomics, the running maximum against which the
+    flash forward rounds P (the emulation rounds against the final one: another
+    sample of the same relative rounding), ``__expf`` / ``__logf``.
+    """
+    if emulate not in (None, "bf16", "f32"):
+        raise ValueError(f"emulate must be None, 'bf16' or 'f32', got {emulate!r}")
+    if kv_lengths is not None and dout is not None:
+        raise ValueError("reference_mha_step with kv_lengths is forward only")
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    same = lambda x: x                                           # noqa: E731
+    if emulate is None:
+        op = io = same
+    else:
+        op = _bf16_round
+        io = _bf16_round if emulate == "bf16" else same
+        q, k, v = (io(t.float()) for t in (q, k, v))
+        dout = None if dout is None else io(dout.float())
+    T = q.shape[2]
+    row = None
+    if kv_lengths is not None:
+        L = kv_lengths.to(q.device).clamp(1, T)
+        valid = torch.arange(T, device=q.device)[None, :] < L[:, None]  # (B, T)
+        row = valid[:, None, :, None]
+        zero = torch.zeros((), dtype=q.dtype, device=q.device)
+        q, k, v = (torch.where(row, t, zero) for t in (q, k, v))
+    qo, ko, vo = op(q), op(k), op(v)
+
+    s = torch.matmul(qo, ko.transpose(-1, -2)) * scale
+    if row is not None:
+        s = s.masked_fill(~valid[:, None, None, :], float("-inf"))
+    if emulate is None:
+        lse = torch.logsumexp(s, dim=-1)
+        p = torch.exp(s - lse[..., None])
+        o = torch.matmul(p, vo)
+    else:
+        m = s.max(dim=-1).values
+        e = torch.exp(s - m[..., None])
+        l = e.sum(dim=-1)
+        o = io(torch.matmul(op(e), vo) / l[..., None])
+        lse = m + torch.log(l)
+    if row is not None:
+        o = torch.where(row, o, zero)
+        lse = torch.where(row[..., 0], lse, zero)
+        return o, lse, None, None, None
+    if dout is None:
+        return o, lse, None, None, None
+
+    douto = op(dout)
+    drow = (dout * o).sum(dim=-1, keepdim=True)
+    if emulate is not None:
+        p = torch.exp(s - lse[..., None])
+    dp = torch.matmul(douto, vo.transpose(-1, -2))
+    ds = op(p * (dp - drow) * scale)
+    dq = io(torch.matmul(ds, ko))
+    dk = io(torch.matmul(ds.transpose(-1, -2), qo))
+    dv = io(torch.matmul(op(p).transpose(-1, -2), douto))
+    return o, lse, dq, dk, dv
+
+
 class _MHAFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale):
